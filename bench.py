@@ -2,6 +2,7 @@
 statistics), BASELINE.json metric, on the C3 workload.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 One step = one pass of the hot path over one batch of reads resident in HBM
@@ -10,7 +11,14 @@ step, so the step prepares it (the direct path: probe_kernel, then K2 reads
 and validates the raw tuples), computes the depth of every contig (K2) with
 the whole-contig region statistics folded in, and finalizes the region table
 (K3b) [+ for N > 1 the RCCL all-gather of the table].  Inputs are generated on
-the GPU before timing (synthetic).
+the GPU before timing (synthetic; the same arguments give the same inputs).
+
+A plain run sets up, warms up, times the K steps, writes its outputs when
+--dump-outputs is given and prints the result line.  --full adds everything
+else the benchmark measures, each after the timed steps and outside `value`:
+the second timed loop on a reused index (`reused_index`), the CPU baselines
+(`cpu_baseline*`, `cpu_interval_count`), for N > 1 one all-gather timed apart
+(`allgather_ms`), and --pcie's host-buffer run.
 
 `--gpus N` without torchrun around it starts `torch.distributed.run` with N
 ranks as a child process.  Default scaling is strong (BASELINE configs[3]):
@@ -23,6 +31,9 @@ import os
 import time
 
 import numpy as np
+
+
+DUMP_DEPTH_POSITIONS = 4 << 20   # --dump-outputs: depth positions written (32 MB of float64)
 
 
 def parse(argv=None):
@@ -47,7 +58,11 @@ def parse(argv=None):
                     help="raw-CIGAR input: ~Poisson(--cigar-ops) BAM CIGAR words per read resident "
                          "in HBM; each step runs K1 (CIGAR -> span) + prepare + K2 + K3b")
     ap.add_argument("--cigar-ops", type=float, default=200.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need (each outside `value`): the timed "
+                         "loop on a reused index, the CPU baselines, for N > 1 one all-gather timed "
+                         "apart, and --pcie")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-sample-bases", type=float, default=3.0e9,
                     help="aligned bases in the CPU-baseline sample (~10-20 s on one core)")
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -55,14 +70,19 @@ def parse(argv=None):
                          "quota, twice it and the affinity set: SURVEY §8 d's all-cores baseline)")
     ap.add_argument("--cpu-parallel-min-s", type=float, default=2.0,
                     help="the all-cores baseline repeats the whole workload until it has run this long")
-    ap.add_argument("--pcie", action="store_true", help="also time host-buffer ingest (H2D)")
+    ap.add_argument("--pcie", action="store_true", help="--full: also time host-buffer ingest (H2D)")
     ap.add_argument("--prepare-steps", type=int, default=None,
-                    help="steps of the second timed loop, which reuses one explicit prepare's index "
-                         "(default: --steps; 0 = skip)")
+                    help="--full: steps of the second timed loop, which reuses one explicit prepare's "
+                         "index (default: --steps; 0 = skip)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dump-rows", default=None, metavar="PATH",
                     help="rank 0 saves the (gathered) region rows of the last step, in region "
                          "order, as a .npy (tests compare them with the oracle)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed as "
+                         "DIR/<name>.npy: region_stats (float64 [regions, 9], the region table in region "
+                         "order) and depth (float64, the per-position depth of a fixed seeded sample of "
+                         "windows; every position when there are at most %d)" % DUMP_DEPTH_POSITIONS)
     ap.add_argument("--exchange-every", type=int, default=8, metavar="G",
                     help="N > 1: the region tables of G consecutive steps leave in one all-gather "
                          "(one collective per step cost the N = 8 share ~20 us of host time per "
@@ -70,7 +90,10 @@ def parse(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend for N > 1 (nccl = RCCL over xGMI; gloo only to "
                          "rehearse several ranks on one GPU)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args, argv):
@@ -281,6 +304,36 @@ def cpu_baseline_interval(lengths, tid, pos, span, sample_bases):
     return {"value": bases / dt, "unit": "aligned bases/s", "cores": 1, "kind": "port",
             "sample": "same %d contigs as cpu_baseline, difference array + counting-sort "
                       "statistics (not the reference algorithm), %.2f s" % (k, dt)}
+
+
+def depth_sample_windows(lengths, budget=DUMP_DEPTH_POSITIONS):
+    """(tid, start, end) windows of the depth vector that --dump-outputs writes:
+    every contig whole when that is at most `budget` positions, otherwise 256
+    windows drawn by a fixed seed (contig by length, start uniform), so two
+    builds run with the same arguments write the same positions."""
+    lengths = np.asarray(lengths, np.int64)
+    if int(lengths.sum()) <= budget:
+        return [(t, 0, int(L)) for t, L in enumerate(lengths)]
+    rng = np.random.default_rng(0)
+    w = budget // 256
+    tids = rng.choice(len(lengths), size=256, p=lengths / lengths.sum())
+    u = rng.random(256)
+    out = []
+    for t, x in zip(tids, u):
+        L = int(lengths[t])
+        n = min(w, L)
+        s = int(x * (L - n + 1))
+        out.append((int(t), s, s + n))
+    return out
+
+
+def dump_outputs(path, rows, depth):
+    """--dump-outputs: rows (the structured region table) as float64 [R, 9]
+    (exact below 2**53) and the sampled depth positions as float64."""
+    os.makedirs(path, exist_ok=True)
+    table = np.stack([rows[f].astype(np.float64) for f in rows.dtype.names], axis=1)
+    np.save(os.path.join(path, "region_stats.npy"), table)
+    np.save(os.path.join(path, "depth.npy"), depth.astype(np.float64))
 
 
 def kernel_source_id(root):
@@ -500,17 +553,22 @@ def main():
     if args.cigar:   # K1 re-derived exactly the generator's spans
         assert bases == int(span.to(torch.int64).sum()), "K1 spans differ from the generator"
     head_direct = paths["direct"] == args.steps
+    depth_dump = None
+    if args.dump_outputs and rank == 0:   # the last timed step's depth, before anything else runs
+        depth_dump = np.concatenate([eng.depth(t, s, e) for t, s, e in depth_sample_windows(lengths)])
+    if not ex:
+        last_table = table.cpu().numpy()
     # ---- the same batch with the index of one explicit prepare() reused by
     # every step (the reference's BAI analog), reported beside the headline
     elapsed_re, re_k = None, None
-    if not args.cigar and args.prepare_steps > 0:
+    if args.full and not args.cigar and args.prepare_steps > 0:
         eng.invalidate()
         eng.prepare()
         step(False)
         elapsed_re, re_k, _ = timed(args.prepare_steps, False)
     # the region-table exchange alone (RCCL all-gather over xGMI), timed apart
     allgather_ms = None
-    if ex:
+    if ex and args.full:
         n_ag = max(5, args.steps)
         sync_all()
         ta = time.perf_counter()
@@ -521,11 +579,11 @@ def main():
     t_max, t_max_re = elapsed, elapsed_re
     total_bases = bases
     if ex:
-        t = torch.tensor([elapsed, elapsed_re or 0.0, allgather_ms], dtype=torch.float64, device=coll_dev)
+        t = torch.tensor([elapsed, elapsed_re or 0.0, allgather_ms or 0.0], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         t_max = float(t[0].item())
         t_max_re = float(t[1].item()) if elapsed_re is not None else None
-        allgather_ms = float(t[2].item())
+        allgather_ms = float(t[2].item()) if allgather_ms is not None else None
         b = torch.tensor([bases], dtype=torch.int64, device=coll_dev)
         dist.all_reduce(b)
         total_bases = int(b.item())
@@ -535,11 +593,13 @@ def main():
         rows = mdist.unpack_rows(full.cpu().numpy(), n_regions_total, REGION_STAT_DTYPE)
         assert int(rows["sum"].sum()) == total_bases, "gathered region table lost bases"
     else:
-        rows = table.cpu().numpy().view(REGION_STAT_DTYPE).reshape(-1)
+        rows = last_table.view(REGION_STAT_DTYPE).reshape(-1)
         if not os.environ.get("MC_BENCH_NOCHECK"):   # set only for deliberately-wrong A/B builds
             assert int(rows["sum"].sum()) == total_bases
     if args.dump_rows and rank == 0:
         np.save(args.dump_rows, rows)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rows, depth_dump)
 
     # roofline of the dominant kernel of the headline step (K2): it reads the
     # raw (tid, pos, span) tuples on the direct path (12 B/read) or the packed
@@ -575,7 +635,7 @@ def main():
 
     if rank == 0:
         cpu = cpu_par = cpu_int = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             h = [x.cpu().numpy() for x in (tid, pos, span)]
             cpu = cpu_baseline(lengths, *h, args.cpu_sample_bases, args.config.upper())
             cpu_par = cpu_baseline_parallel(lengths, *h, cpu_thread_counts(args.cpu_threads),
@@ -583,7 +643,7 @@ def main():
             cpu_int = cpu_baseline_interval(lengths, *h, args.cpu_sample_bases)
             del h
         pcie = None
-        if args.pcie and world == 1:
+        if args.full and args.pcie and world == 1:
             h = [x.cpu().numpy() for x in (tid, pos, span)]
             e2 = CoverageEngine(local)
             e2.set_contigs(lengths)
@@ -649,7 +709,7 @@ def main():
             "world_size": world,
             "ranks_seen": dist.get_world_size() if ex else 1,
             "backend": (args.backend if ex else None),
-            "allgather_ms": allgather_ms,   # one all-gather of a G-step group of region tables
+            "allgather_ms": allgather_ms,   # --full: one all-gather of a G-step group of region tables
             "exchange_every": (G if ex else None),
         }
         if t_max_re is not None:

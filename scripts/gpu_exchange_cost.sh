@@ -11,7 +11,7 @@ for cfg in "0 8" "1 1" "1 8" "0 8" "1 1" "1 8"; do
   set -- $cfg; ex=$1; G=$2
   MC_BENCH_FORCE_EXCHANGE=$ex timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
       --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) bench.py --backend nccl --config c3 \
-      --reads 12500000 --contigs 125 --steps 40 --warmup 5 --prepare-steps 0 --no-cpu-baseline --exchange-every $G > "$O/exch_$ex.log" 2>&1 \
+      --reads 12500000 --contigs 125 --steps 40 --warmup 5 --full --prepare-steps 0 --no-cpu-baseline --exchange-every $G > "$O/exch_$ex.log" 2>&1 \
       || { echo "run ex=$ex failed"; tail -20 "$O/exch_$ex.log"; exit 1; }
   python - "$O/exch_$ex.log" $ex <<'PY'
 import json, sys

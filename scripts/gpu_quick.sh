@@ -14,7 +14,7 @@ fi
 timeout -k 10 200 python scripts/prep_probe.py --config c3 > $O/${TAG}_prep.log 2>&1 || exit $?
 timeout -k 10 200 python scripts/prep_probe.py --config c5 --reps 5 >> $O/${TAG}_prep.log 2>&1 || exit $?
 grep prepare $O/${TAG}_prep.log
-timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > $O/${TAG}_bench.log 2>&1 || { tail -5 $O/${TAG}_bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full ${BENCH_ARGS:-} > $O/${TAG}_bench.log 2>&1 || { tail -5 $O/${TAG}_bench.log; exit 1; }
 python - "$O/${TAG}_bench.log" <<'PY'
 import json,sys
 d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][-1]

@@ -22,12 +22,12 @@ timeout -k 10 ${TEST_TIMEOUT:-900} python -u -m pytest tests -m gpu ${PYTEST_ARG
 s=$?; grep -E "passed|failed|error" $O/${TAG}_pytest_gpu.log | tail -15; faulted $O/${TAG}_pytest_gpu.log; stop_if_fatal $s
 fi
 if [ -z "${SKIP_BENCH:-}" ]; then
-timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > $O/${TAG}_bench.log 2>&1
+timeout -k 10 300 python bench.py --full ${BENCH_ARGS:-} > $O/${TAG}_bench.log 2>&1
 s=$?; tail -2 $O/${TAG}_bench.log; faulted $O/${TAG}_bench.log; stop_if_fatal $s
 fi
 if [ -n "${PROF:-}" ]; then
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_prof.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o run -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/${TAG}_prof.log 2>&1
 s=$?; tail -2 $O/${TAG}_prof.log; faulted $O/${TAG}_prof.log; stop_if_fatal $s
 cd $R
 fi

@@ -27,7 +27,7 @@ for step in ${STEPS:-tests}; do
       TAG=${TAG}_k2 bash "$R/scripts/gpu_ab_r04.sh"; s=$?; fatal $s k2ab ;;
     bench|bench_c2|bench_c5)
       cfg=""; [ $step = bench_c2 ] && cfg="--config c2"; [ $step = bench_c5 ] && cfg="--config c5 --no-cpu-baseline"
-      timeout -k 10 300 python bench.py $cfg ${BENCH_ARGS:-} > "$O/${TAG}_${step}.log" 2>&1
+      timeout -k 10 300 python bench.py --full $cfg ${BENCH_ARGS:-} > "$O/${TAG}_${step}.log" 2>&1
       s=$?; tail -1 "$O/${TAG}_${step}.log" | cut -c1-300; faulted "$O/${TAG}_${step}.log"; fatal $s $step ;;
     smoke)
       timeout -k 10 240 python __graft_entry__.py smoke > "$O/${TAG}_smoke.log" 2>&1

@@ -1091,7 +1091,7 @@ def test_bench_json_contract(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c2", "--steps", "3",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--config", "c2", "--steps", "3",
                           "--warmup", "1", "--prepare-steps", "2", "--cpu-sample-bases", "2e7",
                           "--cpu-threads", "2"],
                          capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
@@ -1116,6 +1116,51 @@ def test_bench_json_contract(tmp_path):
     assert c["value"] > 0 and c["kind"] in ("port", "reference")
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the headline alone: the other legs' keys
+    are empty, and --dump-outputs writes the last step's region table and the
+    seeded sample of its depth vector, equal to the oracle's on the same
+    (regenerated) workload."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    reads, contigs = 300_000, 12                                 # ~12 Mbp: more than the dump's budget
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
+                          "--warmup", "1", "--reads", str(reads), "--contigs", str(contigs),
+                          "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "int32"
+    assert abs(d["value"] - d["config"]["aligned_bases_per_step"] / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+    assert d["cpu_baseline"] is None and d["cpu_baseline_parallel"] is None and d["cpu_interval_count"] is None
+    assert "reused_index" not in d and d["allgather_ms"] is None
+    assert sorted(p.name for p in dump.iterdir()) == ["depth.npy", "region_stats.npy"]
+    import torch
+    sys.path.insert(0, root)
+    import bench
+    lengths, weights = bench.config_contigs("c3", reads, contigs)
+    tid, pos, span, _ = bench.device_workload(torch, lengths, weights, reads, 1, torch.device("cuda", 0))
+    tid, pos, span = (x.cpu().numpy() for x in (tid, pos, span))
+    dd, ext, coff = coracle.depth(lengths, tid, pos, span)
+    want = coracle.region_stats(dd, ext, coff, np.arange(contigs, dtype=np.int32), np.zeros(contigs, np.int64),
+                                lengths.astype(np.int64))
+    got = np.load(dump / "region_stats.npy")
+    assert got.dtype == np.float64 and got.shape == (contigs, 9)
+    for j, f in enumerate(want.dtype.names):
+        assert np.array_equal(got[:, j], want[f].astype(np.float64)), f
+    windows = bench.depth_sample_windows(lengths)
+    assert len(windows) == 256                                   # the sampled path
+    want_d = np.concatenate([dd[coff[t] + s:coff[t] + e] for t, s, e in windows])
+    got_d = np.load(dump / "depth.npy")
+    assert got_d.dtype == np.float64 and np.array_equal(got_d, want_d)
+    assert got_d.nbytes + got.nbytes <= 64 << 20
+
+
 @pytest.mark.parametrize("cfg,reads,contigs", [("c3", 2_000_000, 64), ("c5", 2_000_000, 400)])
 def test_bench_gpus_two_launches_ranks(tmp_path, cfg, reads, contigs):
     """`bench.py --gpus 2` (no torchrun around it) starts two ranks through a
@@ -1132,7 +1177,7 @@ def test_bench_gpus_two_launches_ranks(tmp_path, cfg, reads, contigs):
     env.pop("WORLD_SIZE", None)
     rows_path = str(tmp_path / "rows.npy")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                          "--config", cfg, "--reads", str(reads), "--contigs", str(contigs), "--steps", "2",
+                          "--full", "--config", cfg, "--reads", str(reads), "--contigs", str(contigs), "--steps", "2",
                           "--warmup", "1", "--prepare-steps", "1", "--dump-rows", rows_path],
                          capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -1181,7 +1226,7 @@ def test_bench_rccl_exchange_one_rank(tmp_path):
         port = s.getsockname()[1]
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
-                          os.path.join(root, "bench.py"), "--backend", "nccl", "--config", "c3",
+                          os.path.join(root, "bench.py"), "--backend", "nccl", "--full", "--config", "c3",
                           "--reads", "2000000", "--contigs", "64", "--steps", "6", "--warmup", "2",
                           "--prepare-steps", "2", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
