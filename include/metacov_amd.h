@@ -507,6 +507,25 @@ int mc_bam_rec_chain_host(const uint8_t* d, int64_t n, int64_t q, int32_t n_ref,
  * ranges) -> block count, inflated total, the first cap block offsets. */
 int mc_bgzf_scan_host(const char* path, int n_threads, int64_t* n_blocks, int64_t* inflated,
                       int64_t* offsets, int64_t cap);
+/* Test hook (needs the GPU): the inflate kernel itself, launched as the
+ * resident decode launches it, over n_blocks raw deflate payloads
+ * comp[cdata[i], cdata[i] + clen[i]), block i inflating to
+ * out[out_off[i], out_off[i] + isize[i]).  The device output is filled with
+ * 0xAA before the launch and `out` (a host buffer of out_bytes) receives all
+ * of it, so bytes written outside a block's range are visible.  status[i]:
+ * the kernel's per-block result (0 ok, 1 block type, 2 stored length, 3 code
+ * lengths, 4 code, 5 distance, 6 more output than isize, 7 payload overrun,
+ * 8 fewer bytes than isize; -1: no lane visited the block); a non-zero status
+ * is data, not an error return.  max_lanes: 0 for the decode's own grid, else
+ * the lanes the grid is capped at (fewer lanes than blocks: each lane takes
+ * several blocks in turn), a positive multiple of the kernel's lanes per wave;
+ * the lanes per wave always divide 64, so every multiple of 64 is accepted.
+ * MC_E_INVALID (nothing launched): a payload outside comp, an output range
+ * outside out, overlapping output ranges, a bad max_lanes. */
+int mc_gz_inflate_device(int device, int64_t n_blocks, const uint8_t* comp, int64_t comp_bytes,
+                         const int64_t* cdata, const int32_t* clen, const int64_t* out_off,
+                         const int32_t* isize, uint8_t* out, int64_t out_bytes, int32_t max_lanes,
+                         int32_t* status);
 
 /* ---- synthetic BAM writer ------------------------------------------------
  * Writes coordinate-sorted records from SoA arrays as BGZF-compressed BAM

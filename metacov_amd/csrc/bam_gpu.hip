@@ -2359,6 +2359,72 @@ extern "C" int mc_gz_inflate_host(const uint8_t* src, int64_t clen, uint8_t* dst
     return MC_OK;
 }
 
+// gz_inflate_kernel itself on chosen payloads (GPU unit tests: the device
+// instantiation of inflate.h, byte for byte against zlib).  The launch is the
+// resident decode's (inflate_resident): the same GzBlock table, kPad zero
+// bytes after comp, kGzSlotWords of scratch per lane, lanes / kGzLanes
+// workgroups with lanes = min(max_lanes, n rounded up to kGzLanes).  The
+// device output is filled with 0xAA first and copied back whole, so a caller
+// sees every byte written outside a block's [out_off, out_off + isize); a
+// block no lane visited keeps status -1.  Not a product path.
+static_assert(64 % kGzLanes == 0, "mc_gz_inflate_device documents max_lanes = 64 as always valid");
+extern "C" int mc_gz_inflate_device(int device, int64_t n_blocks, const uint8_t* comp, int64_t comp_bytes,
+                                    const int64_t* cdata, const int32_t* clen, const int64_t* out_off,
+                                    const int32_t* isize, uint8_t* out, int64_t out_bytes, int32_t max_lanes,
+                                    int32_t* status) {
+    MC_REQUIRE(n_blocks >= 0 && comp_bytes >= 0 && out_bytes >= 0 && (comp || comp_bytes == 0) &&
+                   (out || out_bytes == 0),
+               MC_E_INVALID, "bad argument");
+    MC_REQUIRE(n_blocks == 0 || (cdata && clen && out_off && isize && status), MC_E_INVALID, "null block table");
+    MC_REQUIRE(max_lanes >= 0 && max_lanes % kGzLanes == 0, MC_E_INVALID,
+               "max_lanes %d is not 0 or a positive multiple of the %d lanes per wave", (int)max_lanes, kGzLanes);
+    std::vector<GzBlock> hb((size_t)n_blocks);
+    std::vector<std::pair<int64_t, int64_t>> spans;   // the non-empty output ranges
+    for (int64_t i = 0; i < n_blocks; ++i) {
+        MC_REQUIRE(clen[i] >= 0 && cdata[i] >= 0 && cdata[i] <= comp_bytes - clen[i], MC_E_INVALID,
+                   "block %lld: payload [%lld, +%d) outside the %lld compressed bytes", (long long)i,
+                   (long long)cdata[i], (int)clen[i], (long long)comp_bytes);
+        MC_REQUIRE(isize[i] >= 0 && out_off[i] >= 0 && out_off[i] <= out_bytes - isize[i], MC_E_INVALID,
+                   "block %lld: output [%lld, +%d) outside the %lld output bytes", (long long)i,
+                   (long long)out_off[i], (int)isize[i], (long long)out_bytes);
+        if (isize[i]) spans.emplace_back(out_off[i], out_off[i] + isize[i]);
+        hb[(size_t)i] = GzBlock{cdata[i], out_off[i], clen[i], isize[i]};
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t k = 1; k < spans.size(); ++k)
+        MC_REQUIRE(spans[k - 1].second <= spans[k].first, MC_E_INVALID,
+                   "output ranges [%lld, %lld) and [%lld, %lld) overlap", (long long)spans[k - 1].first,
+                   (long long)spans[k - 1].second, (long long)spans[k].first, (long long)spans[k].second);
+    HIP_TRY(hipSetDevice(device));
+    DBuf<uint8_t> dcomp, dout;
+    HIP_TRY(dout.reserve((size_t)out_bytes + 1));
+    HIP_TRY(hipMemset(dout.p, 0xAA, (size_t)out_bytes));
+    if (n_blocks) {
+        const int64_t cap = max_lanes ? max_lanes : gz_max_lanes(device);
+        const int64_t lanes = std::min<int64_t>(cap, (n_blocks + kGzLanes - 1) / kGzLanes * kGzLanes);
+        DBuf<GzBlock> dblk;
+        DBuf<int> dstatus;
+        DBuf<uint16_t> dscratch;
+        HIP_TRY(dcomp.reserve((size_t)comp_bytes + kPad));
+        HIP_TRY(dblk.reserve((size_t)n_blocks));
+        HIP_TRY(dstatus.reserve((size_t)n_blocks + 1));
+        HIP_TRY(dscratch.reserve((size_t)(lanes * kGzSlotWords)));
+        if (comp_bytes) HIP_TRY(hipMemcpy(dcomp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(dcomp.p + comp_bytes, 0, kPad));
+        HIP_TRY(hipMemcpy(dblk.p, hb.data(), (size_t)n_blocks * sizeof(GzBlock), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(dstatus.p, 0xFF, (size_t)n_blocks * sizeof(int)));
+        HIP_TRY(hipMemset(dstatus.p + n_blocks, 0, sizeof(int)));
+        gz_inflate_kernel<<<(int)(lanes / kGzLanes), kGzThreads, 0, nullptr>>>(
+            dcomp.p, dblk.p, n_blocks, dout.p, dscratch.p, dstatus.p, dstatus.p + n_blocks);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        static_assert(sizeof(int) == sizeof(int32_t), "status words");
+        HIP_TRY(hipMemcpy(status, dstatus.p, (size_t)n_blocks * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    if (out_bytes) HIP_TRY(hipMemcpy(out, dout.p, (size_t)out_bytes, hipMemcpyDeviceToHost));
+    return MC_OK;
+}
+
 // The GPU decode's BGZF block scan on the host (unit tests): block count,
 // inflated total and up to cap block offsets.
 extern "C" int mc_bgzf_scan_host(const char* path, int n_threads, int64_t* n_blocks, int64_t* inflated,

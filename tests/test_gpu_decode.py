@@ -6,7 +6,10 @@ and on the BGZF blocks of the fixture and synthetic BAMs; the record parse
 against the host decoder's rules.  GPU tests: mc_bam_gpu_open against the
 host decoder (mc_bam_open, itself pinned by the goldens in test_decoder.py)
 record for record, including windows far smaller than one record, records
-spanning many 64 KiB parse segments, and the error classes.
+spanning many 64 KiB parse segments, the error classes, and hand-framed
+files whose neighbouring BGZF blocks differ in deflate block type and size
+(and an all-stored one).  The inflate kernel's own bytes against zlib:
+test_gpu_inflate.py.
 """
 import ctypes
 import os
@@ -28,6 +31,17 @@ def _lib():
 def _raw_deflate(data, level, strategy=zlib.Z_DEFAULT_STRATEGY):
     c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
     return c.compress(data) + c.flush()
+
+
+def _flushed(data, level, mode, every=7000, strategy=zlib.Z_DEFAULT_STRATEGY):
+    """A raw deflate stream of several blocks: one (or more) per `every`
+    bytes, each closed by a sync or full flush (an empty stored block), then
+    the final block."""
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+    out = b""
+    for i in range(0, len(data), every):
+        out += c.compress(data[i:i + every]) + c.flush(mode)
+    return out + c.flush()
 
 
 def _inflate_host(comp, isize):
@@ -87,6 +101,29 @@ def test_inflate_host_matches_zlib(lib_built):
                 comp = _raw_deflate(data, level, strat)
                 rc, got = _inflate_host(comp, len(data))
                 assert rc == 0 and got == data, (len(data), level, strat)
+    # ISIZE 65536 (level 0: two stored blocks in one payload), and payloads of
+    # several deflate blocks: a sync or full flush every 7000 bytes, and a
+    # sync flush before finish (an empty stored block before the final block)
+    big = [_rare_matches(3, 65536), bytes(rng.integers(0, 256, 65536, dtype=np.uint8)),
+           bytes(rng.choice(np.frombuffer(b"ACGTN", np.uint8), 65536, p=[.3, .2, .2, .29, .01])), b"x" * 65536]
+    for data in big:
+        for level in (0, 1, 6, 9):
+            for strat in (zlib.Z_DEFAULT_STRATEGY, zlib.Z_FIXED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE):
+                comp = _raw_deflate(data, level, strat)
+                rc, got = _inflate_host(comp, len(data))
+                assert rc == 0 and got == data, (len(data), level, strat)
+    for data in cases + big:
+        for level, strat in ((0, zlib.Z_DEFAULT_STRATEGY), (1, zlib.Z_DEFAULT_STRATEGY), (6, zlib.Z_DEFAULT_STRATEGY),
+                             (9, zlib.Z_FIXED), (6, zlib.Z_RLE)):
+            for mode in (zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH):
+                comp = _flushed(data, level, mode, strategy=strat)
+                assert zlib.decompress(comp, -15) == data
+                rc, got = _inflate_host(comp, len(data))
+                assert rc == 0 and got == data, (len(data), level, strat, mode)
+        c = zlib.compressobj(6, zlib.DEFLATED, -15, 8)
+        comp = c.compress(data) + c.flush(zlib.Z_SYNC_FLUSH) + c.flush()
+        rc, got = _inflate_host(comp, len(data))
+        assert rc == 0 and got == data, len(data)
     # wrong ISIZE either way is an error
     comp = _raw_deflate(b"x" * 1000, 6)
     assert _inflate_host(comp, 999)[0] != 0
@@ -680,3 +717,142 @@ def test_classic_path_decodes_on_the_gpu(lib_built, golden_dir, fixture_golden):
         pileup.close_all()
     assert got == {"min": 7, "max": 526, "med": 344, "std": 134.03, "avg": 342.53, "q23": 353.25,
                    "sum": 145231}
+
+
+# ------------------------------------------------ hand-framed BGZF blocks
+
+def _bgzf_frame(chunk, level, strategy=zlib.Z_DEFAULT_STRATEGY, extra=None, extra_first=False):
+    """One BGZF block framed by hand (as synth._bgzf_block) from the raw
+    chunk and its compress parameters; extra: a second extra subfield
+    (SI1 SI2 SLEN data) before or after the BC one."""
+    cdata = _raw_deflate(chunk, level, strategy)
+    bc = struct.pack("<BBHH", 66, 67, 2, 0)
+    xlen = len(bc) + len(extra or b"")
+    bsize = 12 + xlen + len(cdata) + 8
+    assert bsize <= 65536, (len(chunk), level, strategy, bsize)
+    bc = struct.pack("<BBHH", 66, 67, 2, bsize - 1)
+    sub = bc if not extra else (extra + bc if extra_first else bc + extra)
+    return (struct.pack("<BBBBIBBH", 31, 139, 8, 4, 0, 0, 255, xlen) + sub + cdata +
+            struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+
+
+_FRAMINGS = [(0, zlib.Z_DEFAULT_STRATEGY), (6, zlib.Z_FIXED), (1, zlib.Z_DEFAULT_STRATEGY),
+             (9, zlib.Z_DEFAULT_STRATEGY), (6, zlib.Z_RLE), (6, zlib.Z_HUFFMAN_ONLY)]
+_framing_cache = {}
+
+
+def _framing_stream():
+    """A BAM's inflated bytes (header + ~11 k records of edge_mix_records with
+    random bases, ~3 MB) and the records alone."""
+    if "stream" not in _framing_cache:
+        rng = np.random.default_rng(31)
+        names, lengths = ["a", "b", "c"], [3_000_000, 1_000, 900_000]
+        recs = synth.edge_mix_records(lengths, 11_000, seed=31, unplaced=40)
+        acgt = np.frombuffer(b"ACGTN", np.uint8)
+        for r in recs:
+            r.seq = acgt[rng.choice(5, r.l_seq, p=[.3, .2, .2, .29, .01])].tobytes().decode()
+        text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % x for x in zip(names, lengths))
+        hdr = bytearray(b"BAM\x01") + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(names))
+        for nm, L in zip(names, lengths):
+            hdr += struct.pack("<i", len(nm) + 1) + nm.encode() + b"\0" + struct.pack("<i", L)
+        _framing_cache["stream"] = (bytes(hdr), [synth.encode_record(r) for r in recs])
+    return _framing_cache["stream"]
+
+
+def _mixed_framing_bam(path):
+    """The stream cut at random places (records straddle every block edge)
+    into blocks that cycle through stored, fixed, dynamic level 1 / 9, RLE
+    and Huffman-only, of 1 - 65280 bytes (the kinds that can expand their
+    input: up to 49152, so BSIZE fits), with three empty blocks, two blocks
+    carrying a second extra subfield (XLEN 10; before and after BC) and one
+    block of ISIZE 65536 in the middle of the file.  Returns the block count."""
+    hdr, recs = _framing_stream()
+    data = hdr + b"".join(recs)
+    assert len(data) > 2_800_000
+    rng = np.random.default_rng(32)
+    out, o, k = bytearray(), 0, 0
+    sizes = []
+    while o < len(data):
+        level, strat = _FRAMINGS[k % len(_FRAMINGS)]
+        cap = 65280 if strat == zlib.Z_DEFAULT_STRATEGY else 49152
+        n = int(rng.integers(1, cap + 1)) if k % 9 else int(rng.integers(1, 40))
+        extra, first = None, False
+        if k == 20:
+            n, level, strat = 65536, 6, zlib.Z_DEFAULT_STRATEGY
+        if k in (12, 30):
+            extra, first = struct.pack("<BBH", 88, 89, 0), k == 12
+        if k in (25, 26, 40):
+            n = 0
+        chunk = data[o:o + n]
+        out += _bgzf_frame(chunk, level, strat, extra, first)
+        sizes.append(len(chunk))
+        o += len(chunk)
+        k += 1
+    assert k >= 64 and sizes[20] == 65536 and sizes[25] == sizes[26] == sizes[40] == 0
+    with open(path, "wb") as fh:
+        fh.write(bytes(out) + synth._BGZF_EOF)
+    return k
+
+
+def _uncompressed_bam(path, repeat=18):
+    """`samtools view -u`: the same records (each `repeat` times in place:
+    ~200 k records, still sorted), every block stored."""
+    hdr, recs = _framing_stream()
+    data = hdr + b"".join(r * repeat for r in recs)
+    with open(path, "wb") as fh:
+        for i in range(0, len(data), 0xff00):
+            fh.write(_bgzf_frame(data[i:i + 0xff00], 0))
+        fh.write(synth._BGZF_EOF)
+    return (len(data) + 0xff00 - 1) // 0xff00
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("window", [0, 1 << 18])
+def test_gpu_decode_mixed_framing(lib_built, tmp_path, window):
+    """Blocks of every deflate block type and of 0 - 65536 bytes side by
+    side in one file (a wave's lanes hold different types at once), against
+    the host decoder and the oracle's reader."""
+    p = str(tmp_path / "mixed.bam")
+    nb = _mixed_framing_bam(p)
+    h, g = _host_and_gpu(p, window_bytes=window)
+    _assert_same(h, g)
+    _assert_oracle(p, g)
+    t = g.timings()
+    assert t["blocks"] == nb + 1 and t["resyncs"] <= 64, t
+    if window:
+        assert t["windows"] > 1
+    g.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("window", [0, 1 << 18])
+def test_gpu_decode_uncompressed_bam(lib_built, tmp_path, window):
+    """Uncompressed BAM (every block stored), a few hundred blocks."""
+    p = str(tmp_path / "u.bam")
+    nb = _uncompressed_bam(p)
+    assert nb > 200
+    h, g = _host_and_gpu(p, window_bytes=window)
+    assert h.n_records > 190_000
+    _assert_same(h, g)
+    _assert_oracle(p, g)
+    t = g.timings()
+    assert t["blocks"] == nb + 1 and t["resyncs"] <= 64, t
+    g.close()
+
+
+@pytest.mark.gpu
+def test_scan_gpu_decode_mixed_framing(lib_built, tmp_path):
+    """`scan` reads the sequence bytes: its tables over the mixed-framing file
+    decoded on the GPU equal the host source's."""
+    from metacov_amd import scan as mscan
+    p = str(tmp_path / "mixed.bam")
+    _mixed_framing_bam(p)
+    outs = []
+    for decode in ("host", "gpu"):
+        c = mscan.ByFlag([mscan.BaseHist(2), mscan.KmerHist(5, 6, 4, 1), mscan.MirrorHist(4, 10),
+                          mscan.IsizeHist()], [mscan.Flags["IsRead1"], mscan.Flags["Readdir"]])
+        n = mscan.scan_reads(p, None, c, decode=decode)
+        rows = [[list(map(str, r)) for r in q.get_rows()] for g in c.processors for q in g.processors]
+        outs.append((n, rows))
+    assert outs[0][0] == outs[1][0] == 11_040
+    assert outs[0][1] == outs[1][1]
