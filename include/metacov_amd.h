@@ -254,6 +254,49 @@ int mc_max_depth(mc_ctx* ctx, int32_t* out);
 int mc_get_timings(mc_ctx* ctx, mc_timings* out);
 int mc_synchronize(mc_ctx* ctx);
 
+/* ---- per-base depth as runs (csrc/runs.hip) --------------------------------
+ * The depth vector run-length encoded on the device: what bedtools genomecov
+ * -bg/-bga, mosdepth and samtools depth write as (contig, start, end, depth)
+ * lines (nothing in the reference, whose pileup reports the nine statistics
+ * only).  Depths are exact: the pileup read cap (below) is a per-query
+ * artefact and is not applied.
+ *
+ * mc_runs_compute: for each of S segments [start, end) of contig tid, in
+ * input order, the maximal runs of equal q(depth).  Segments may be unsorted,
+ * overlapping, duplicated or empty and may run past the contig's extent
+ * (those positions have depth 0, as in mc_get_depth, and take part like any
+ * value: zero runs are kept).  q(d) = d with n_edges = 0; else the number of
+ * edges <= d (n_edges <= 16 strictly increasing non-negative edges; 1, 4, 100
+ * are mosdepth's --quantize 0:1:4:100:).  Run i starts at run_start[i]
+ * (relative to the contig) with value run_value[i] and ends where the next
+ * run of its segment starts, or at the segment's end; segment s owns runs
+ * [seg_first[s], seg_first[s + 1]) (none when it is empty).  A run never
+ * crosses a segment boundary.  *n_runs = seg_first[S].
+ *
+ * The ctx's depth must be computed (MC_E_STATE) on the handle's device
+ * (MC_E_INVALID, as for a bad tid, range or edge list).  The call waits for
+ * the ctx (mc_synchronize), then runs on the handle's own stream: one count
+ * pass and one emit pass over the segments' depth (two reads of 4 B per
+ * position), an exclusive scan of the per-tile counts between them.  Results
+ * stay in device memory owned by the handle (12 B per run; buffers only grow
+ * and are reused) until the next mc_runs_compute or mc_runs_destroy.
+ * mc_runs_get copies runs [first, first + count) to the host
+ * (MC_E_INVALID outside [0, n_runs]); mc_runs_device exposes the arrays to
+ * zero-copy consumers.  mc_runs_timing: HIP-event times of the three launches
+ * of the last compute and its tile count.  mc_runs_dims (test hook): the tile
+ * size and the tiles the scan takes per iteration. */
+typedef struct mc_runs mc_runs;
+int mc_runs_create(int device, mc_runs** out);
+int mc_runs_destroy(mc_runs* r);
+int mc_runs_compute(mc_runs* r, mc_ctx* ctx, int64_t S, const int32_t* tid, const int64_t* start,
+                    const int64_t* end, int32_t n_edges, const int32_t* edges, int64_t* n_runs);
+int mc_runs_seg_first(const mc_runs* r, int64_t* seg_first /* S + 1 */);
+int mc_runs_get(const mc_runs* r, int64_t first, int64_t count, int64_t* run_start, int32_t* run_value);
+int mc_runs_device(const mc_runs* r, const int64_t** d_start, const int32_t** d_value,
+                   const int64_t** d_seg_first, int64_t* n_runs);
+int mc_runs_timing(const mc_runs* r, float* count_ms, float* scan_ms, float* emit_ms, int64_t* tiles);
+int mc_runs_dims(int32_t* tile, int32_t* scan_width);
+
 /* ---- htslib's pileup read cap (opt-in) -----------------------------------
  * pysam's AlignmentFile.pileup(ref, start, end) (pileup.py:13) runs htslib's
  * pileup with max_depth = 8000: bam_plp_push drops a read that starts where

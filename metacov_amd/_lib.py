@@ -116,6 +116,16 @@ SIGNATURES = {
     "mc_max_depth": [_P, _PI32],
     "mc_get_timings": [_P, ctypes.POINTER(Timings)],
     "mc_synchronize": [_P],
+    # per-base depth as runs (csrc/runs.hip)
+    "mc_runs_create": [ctypes.c_int, _PP],
+    "mc_runs_destroy": [_P],
+    "mc_runs_compute": [_P, _P, _I64, _P, _P, _P, _I32, _P, _PI64],
+    "mc_runs_seg_first": [_P, _P],
+    "mc_runs_get": [_P, _I64, _I64, _P, _P],
+    "mc_runs_device": [_P, _PP, _PP, _PP, _PI64],
+    "mc_runs_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                       ctypes.POINTER(ctypes.c_float), _PI64],
+    "mc_runs_dims": [_PI32, _PI32],
     "mc_depth_cap_mask": [_I64, _P, _P, _P, _I32, ctypes.c_int, _P, _PI64],
     "mc_depth_cap_mask_device": [ctypes.c_int, _I64, _P, _P, _P, _I32, _P, _PI64],
     "mc_add_reads_capped": [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I32, _PI64],

@@ -15,6 +15,14 @@ carries pileup.experimental's 13 columns (cli.py:81, :93-95; SURVEY.md §8 f):
 the read side runs on host threads, the k-mer correlation against `-f` on
 the GPU (metacov_amd/experimental.py).
 
+Per-base output (no counterpart in the reference):
+
+    python -m metacov_amd.cli depth -b X.bam [-o out.bedgraph] [-rc R.csv | -rb R.blast7]
+                                    [--quantize 0:1:4:100:] [--no-zero]
+
+writes the exact depth as bedGraph runs, run-length encoded on the GPU
+(metacov_amd/runs.py); one process, no read cap.
+
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
     python -m torch.distributed.run --nproc-per-node 8 -m metacov_amd.cli pileup -b X.bam ...
@@ -482,6 +490,103 @@ def _pileup_shard(path, regionfile_blast7, regionfile_csv, rank, world, device,
     # (contigs, extents) for this rank's -k read table: a contig-subset GPU decode
     shard = (shards[rank], ext) if decode == "gpu" and (have_index or ext is not None) else (None, None)
     return head, regions, tids, starts, ends, rows, std, mine, r_max, region_err, shard
+
+
+DEPTH_GROUP_POSITIONS = 1 << 28     # positions per mc_runs_compute of `depth`
+
+
+def depth_groups(starts, ends, limit=DEPTH_GROUP_POSITIONS):
+    """Consecutive segment ranges [a, b) whose lengths total at most `limit`
+    positions; a single longer segment goes alone."""
+    a, total = 0, 0
+    for i, n in enumerate((np.asarray(ends, np.int64) - np.asarray(starts, np.int64)).tolist()):
+        if i > a and total + n > limit:
+            yield a, i
+            a, total = i, 0
+        total += n
+    if a < len(starts):
+        yield a, len(starts)
+
+
+def write_depth(bam, tids, starts, ends, outfile, device=0, quantize=None, zero=True):
+    """The runs of the segments (header contig ids) as bedGraph lines, group
+    by group, each written before the next is computed."""
+    from . import runs as _runs
+    edges, labels = _runs.parse_quantize(quantize) if quantize else (None, None)
+    if len(tids) == 0:
+        return 0
+    eng = bam.engine(device)
+    local = np.asarray(bam.local_tid(tids), np.int32)
+    names = [w.split()[0] if w.split() else w for w in bam.references]
+    written = 0
+    for a, b in depth_groups(starts, ends):
+        r = eng.depth_runs(local[a:b], starts[a:b], ends[a:b], quantize=edges)
+        r.tids = np.asarray(tids[a:b], np.int32)        # header ids, for the names
+        written += _runs.write_bedgraph(r, names, outfile, zero=zero, labels=labels)
+    return written
+
+
+@main.command()
+@click.option('--bamfile', '-b', type=click.File('rb'), required=True,
+              help="Input BAM file. Must be coordinate-sorted.")
+@click.option('--outfile', '-o', type=click.File('w'), default="-",
+              help="Output bedGraph (default STDOUT)")
+@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
+              help="Input Region file in BLAST7 format")
+@click.option('--regionfile-csv', '-rc', type=click.File('r'),
+              help="Input Region file in CSV format")
+@click.option('--quantize', metavar="SPEC",
+              help="Depth classes in mosdepth's form, e.g. 0:1:4:100: (classes 0:1, 1:4, 4:100, "
+                   "100:inf); the value column is the class label, runs merge per class")
+@click.option('--zero/--no-zero', default=True,
+              help="Write zero-depth runs (default; with --quantize: runs of the first class)")
+@click.option('--device', type=int, default=0, help="HIP device ordinal")
+@click.option('--decode', type=click.Choice(['gpu', 'host']), default='gpu',
+              help="gpu (default): BGZF inflate and record parse on the device; "
+                   "host: the C++ decoder on host threads")
+@click.option('--legacy-endpos', is_flag=True, default=False,
+              help="Count a mapped read without reference-consuming CIGAR ops on one column "
+                   "(htslib <= 1.9 bam_endpos); default: it adds nothing (current htslib)")
+def depth(bamfile, outfile, regionfile_blast7, regionfile_csv, quantize, zero, device, decode,
+          legacy_endpos):
+    """
+    Write per-base depth as bedGraph runs
+
+    One line `contig start end depth` per maximal run of equal depth,
+    run-length encoded on the GPU: every contig in header order over its
+    whole length, or the regions of a region file in file order.  Depths are
+    exact: the htslib read cap that `pileup` applies per region query is not
+    applied here.  Single process only.
+    """
+    from . import runs as _runs
+    if regionfile_blast7 and regionfile_csv:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    if quantize:
+        try:
+            _runs.parse_quantize(quantize)
+        except ValueError as e:
+            raise click.BadParameter(str(e), param_hint="--quantize")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("depth runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)")
+    if decode == 'gpu':
+        bam = GpuBamFile(bamfile.name, device=device, legacy_endpos=legacy_endpos)
+    else:
+        bam = BamFile(bamfile.name, legacy_endpos=legacy_endpos)
+    log_counts(bam)
+    err = None
+    if regionfile_blast7 or regionfile_csv:
+        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, bam)
+        _, tids, starts, ends, err = resolve_regions(bam, regions)
+    else:
+        tids = np.arange(len(bam.lengths), dtype=np.int32)
+        starts = np.zeros(len(tids), np.int64)
+        ends = np.asarray(bam.lengths, np.int64)
+    n = write_depth(bam, tids, starts, ends, outfile, device=device, quantize=quantize, zero=zero)
+    outfile.flush()
+    log.info("%d runs written", n)
+    if err is not None:      # the regions before a failing one are written first, as pileup does
+        raise err
 
 
 @main.command()

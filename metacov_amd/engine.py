@@ -6,6 +6,7 @@
     eng.compute_depth()                    # K2 on the GPU
     eng.depth(tid, start, end)             # int32 numpy
     eng.region_stats(tids, starts, ends)   # structured numpy, exact integers
+    eng.depth_runs(tids, starts, ends)     # runs of equal depth (bedGraph form), encoded on the GPU
     classic_stats(row)                     # -> the dict pileup.classic returns
 
 The statistics formatting here is the host half of the reference's
@@ -129,9 +130,13 @@ class CoverageEngine:
         self.device = int(device)
         self.lengths = np.zeros(0, dtype=np.int64)
         self._rcache = None   # the last region arrays passed as-is and their C arguments
+        self._runs = None     # the mc_runs handle of depth_runs(), made on first use
 
     # -- lifecycle
     def close(self):
+        if getattr(self, "_runs", None) is not None:
+            self._runs.close()
+            self._runs = None
         if getattr(self, "_h", None):
             self._lib.mc_ctx_destroy(self._h)
             self._h = None
@@ -262,6 +267,18 @@ class CoverageEngine:
         out = np.empty(max(0, end - start), dtype=np.int32)
         self._check(self._lib.mc_get_depth(self._h, int(tid), int(start), int(end), ptr(out)))
         return out
+
+    def depth_runs(self, tids=None, starts=None, ends=None, quantize=None):
+        """The computed depth as runs of equal value (metacov_amd.runs.DepthRuns),
+        run-length encoded on the GPU: for each segment [starts[i], ends[i])
+        of contig tids[i], in order (default: every contig over [0, length);
+        starts default to 0, ends to the contig lengths).  Segments may
+        overlap, repeat, be empty or run past the contig (depth 0 there).
+        quantize: None, a mosdepth spec ("0:1:4:100:") or up to 16 strictly
+        increasing edges; the values are then classes (edges <= depth).
+        Depths are exact (no pileup cap)."""
+        from . import runs as _runs
+        return _runs.depth_runs(self, tids, starts, ends, quantize)
 
     def depth_device(self):
         p = ctypes.c_void_p()
