@@ -297,6 +297,70 @@ int mc_runs_device(const mc_runs* r, const int64_t** d_start, const int32_t** d_
 int mc_runs_timing(const mc_runs* r, float* count_ms, float* scan_ms, float* emit_ms, int64_t* tiles);
 int mc_runs_dims(int32_t* tile, int32_t* scan_width);
 
+/* ---- windowed coverage (csrc/windows.hip) ----------------------------------
+ * The form between the nine statistics per region and the per-base runs: the
+ * depth sum and threshold counts of fixed windows (mosdepth --by / --thresholds,
+ * deepTools bins, CoverM's covered fraction) and the depth histogram per
+ * segment (mosdepth's *.dist.txt).  One streaming read of the depth vector
+ * each; integer only, exact and identical from call to call.  Nothing in the
+ * reference.  Depths are exact (no pileup read cap).
+ *
+ * Segments are mc_runs_compute's: unsorted, overlapping, duplicated or empty
+ * ones are fine, positions past the contig's extent have depth 0 and count
+ * like any value; a bad tid, start < 0, end < start or end > 2^40 is
+ * MC_E_INVALID (the message names the segment), as is a ctx on another
+ * device; MC_E_STATE before the ctx's depth is computed.
+ *
+ * mc_windows_compute: segment s is cut into the windows
+ * [start + k window, min(start + (k + 1) window, end)), k = 0 .. ceil(len /
+ * window) - 1; window == 0: one window per non-empty segment, the whole of
+ * it.  An empty segment owns no window.  Segment s owns windows [seg_first[s],
+ * seg_first[s + 1]) (arithmetic, computed on the host, kept on the device for
+ * mc_windows_device); *n_windows = seg_first[S] (more than 2^31: MC_E_RANGE).
+ * Per window: sum, the exact int64 sum of its depths, and ge[j], the number of
+ * its positions with depth >= thr[j] (0 <= n_thr <= 16 non-negative, strictly
+ * increasing thresholds, else MC_E_INVALID; with n_thr == 0 ge may be NULL).
+ * window is 0 or at least MC_WINDOWS_MIN (else MC_E_INVALID): below 16
+ * positions a window's record is larger than the depth values it summarises,
+ * and the runs above are the right output.  The call waits for the ctx
+ * (mc_synchronize), then runs on the handle's own stream: one pass over the
+ * segments' depth (4 B per position read once; a window inside one tile is
+ * finished there, a longer one leaves a partial row per tile) and a combine
+ * pass over the partial rows.  Results stay in device memory owned by the
+ * handle (8 (1 + n_thr) B per window; buffers only grow and are reused) until
+ * the next mc_windows_compute or mc_windows_destroy.  mc_windows_get copies
+ * windows [first, first + count) to the host (MC_E_INVALID outside [0,
+ * n_windows]); mc_windows_device exposes the arrays to zero-copy consumers.
+ *
+ * mc_windows_hist: hist[s][b], b < n_bins - 1, is the number of positions of
+ * segment s with depth == b; the last bin counts depth >= n_bins - 1; every row
+ * sums to end - start.  1 <= n_bins <= max_bins (mc_windows_dims; else
+ * MC_E_INVALID); S n_bins above 2^27 is MC_E_RANGE.  Independent of
+ * mc_windows_compute, whose results it leaves in place.
+ *
+ * mc_windows_timing: HIP-event times of the last compute's two launches and
+ * of the last histogram launch, and the last compute's tile count (MC_E_STATE
+ * before either ran).  mc_windows_dims (test hook): the tile size,
+ * MC_WINDOWS_MIN, the bins the LDS layout affords, and the histogram's fixed
+ * workgroup count. */
+#define MC_WINDOWS_MIN 16
+typedef struct mc_windows mc_windows;
+int mc_windows_create(int device, mc_windows** out);
+int mc_windows_destroy(mc_windows* w);
+int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const int32_t* tid, const int64_t* start,
+                       const int64_t* end, int64_t window, int32_t n_thr, const int32_t* thr,
+                       int64_t* n_windows);
+int mc_windows_seg_first(const mc_windows* w, int64_t* seg_first /* S + 1 */);
+int mc_windows_get(const mc_windows* w, int64_t first, int64_t count, int64_t* sum /* count */,
+                   int64_t* ge /* count x n_thr, row-major */);
+int mc_windows_device(const mc_windows* w, const int64_t** d_sum, const int64_t** d_ge,
+                      const int64_t** d_seg_first, int64_t* n_windows, int32_t* n_thr);
+int mc_windows_hist(mc_windows* w, mc_ctx* ctx, int64_t S, const int32_t* tid, const int64_t* start,
+                    const int64_t* end, int32_t n_bins, int64_t* hist /* host, S x n_bins */);
+int mc_windows_timing(const mc_windows* w, float* window_ms, float* combine_ms, float* hist_ms,
+                      int64_t* tiles);
+int mc_windows_dims(int32_t* tile, int32_t* min_window, int32_t* max_bins, int32_t* hist_groups);
+
 /* ---- htslib's pileup read cap (opt-in) -----------------------------------
  * pysam's AlignmentFile.pileup(ref, start, end) (pileup.py:13) runs htslib's
  * pileup with max_depth = 8000: bam_plp_push drops a read that starts where

@@ -126,6 +126,17 @@ SIGNATURES = {
     "mc_runs_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                        ctypes.POINTER(ctypes.c_float), _PI64],
     "mc_runs_dims": [_PI32, _PI32],
+    # windowed coverage (csrc/windows.hip)
+    "mc_windows_create": [ctypes.c_int, _PP],
+    "mc_windows_destroy": [_P],
+    "mc_windows_compute": [_P, _P, _I64, _P, _P, _P, _I64, _I32, _P, _PI64],
+    "mc_windows_seg_first": [_P, _P],
+    "mc_windows_get": [_P, _I64, _I64, _P, _P],
+    "mc_windows_device": [_P, _PP, _PP, _PP, _PI64, _PI32],
+    "mc_windows_hist": [_P, _P, _I64, _P, _P, _P, _I32, _P],
+    "mc_windows_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                          ctypes.POINTER(ctypes.c_float), _PI64],
+    "mc_windows_dims": [_PI32, _PI32, _PI32, _PI32],
     "mc_depth_cap_mask": [_I64, _P, _P, _P, _I32, ctypes.c_int, _P, _PI64],
     "mc_depth_cap_mask_device": [ctypes.c_int, _I64, _P, _P, _P, _I32, _P, _PI64],
     "mc_add_reads_capped": [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I32, _PI64],

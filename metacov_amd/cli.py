@@ -23,6 +23,15 @@ Per-base output (no counterpart in the reference):
 writes the exact depth as bedGraph runs, run-length encoded on the GPU
 (metacov_amd/runs.py); one process, no read cap.
 
+Windowed output (no counterpart in the reference either):
+
+    python -m metacov_amd.cli coverage -b X.bam [-o out.bed] [-rc R.csv | -rb R.blast7] [--by 500]
+                                       [--thresholds 1,10,30] [--dist out.dist.txt [--dist-bins 1024]]
+
+writes the mean depth per contig, region or fixed window, the positions at or
+above each threshold, and the cumulative depth distribution, all reduced on
+the GPU (metacov_amd/windows.py); one process, no read cap.
+
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
     python -m torch.distributed.run --nproc-per-node 8 -m metacov_amd.cli pileup -b X.bam ...
@@ -586,6 +595,122 @@ def depth(bamfile, outfile, regionfile_blast7, regionfile_csv, quantize, zero, d
     outfile.flush()
     log.info("%d runs written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
+        raise err
+
+
+HIST_GROUP_CELLS = 1 << 27          # segments x bins per mc_windows_hist of `coverage`
+
+
+def write_coverage(bam, tids, starts, ends, outfile, device=0, by=0, thresholds=None, dist=None,
+                   dist_bins=1024, labels=None):
+    """The windows of the segments (header contig ids) as a table, group by
+    group, each written before the next is computed; with `dist` also the
+    cumulative depth distribution per segment (labels) and in total."""
+    from . import windows as _windows
+    thr = _windows.parse_thresholds(thresholds) if thresholds else []
+    names = [w.split()[0] if w.split() else w for w in bam.references]
+    if len(tids) == 0:
+        _windows.write_windows_bed(_windows.WindowCoverage([], [], [], by, thr, [0], [], []), names, outfile)
+        if dist is not None:
+            _windows.write_dist(np.zeros((0, dist_bins), np.int64), [], dist)
+        return 0
+    eng = bam.engine(device)
+    local = np.asarray(bam.local_tid(tids), np.int32)
+    written = 0
+    hists = []
+    per_call = max(1, HIST_GROUP_CELLS // dist_bins)
+    for a, b in depth_groups(starts, ends):
+        wc = eng.depth_windows(local[a:b], starts[a:b], ends[a:b], window=by, thresholds=thr)
+        wc.tids = np.asarray(tids[a:b], np.int32)       # header ids, for the names
+        written += _windows.write_windows_bed(wc, names, outfile, header=a == 0)
+        if dist is not None:
+            for c in range(a, b, per_call):
+                d = min(b, c + per_call)
+                hists.append(eng.depth_hist(local[c:d], starts[c:d], ends[c:d], n_bins=dist_bins))
+    if dist is not None:
+        _windows.write_dist(np.concatenate(hists), labels, dist)
+    return written
+
+
+@main.command()
+@click.option('--bamfile', '-b', type=click.File('rb'), required=True,
+              help="Input BAM file. Must be coordinate-sorted.")
+@click.option('--outfile', '-o', type=click.File('w'), default="-",
+              help="Output windows table (default STDOUT)")
+@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
+              help="Input Region file in BLAST7 format")
+@click.option('--regionfile-csv', '-rc', type=click.File('r'),
+              help="Input Region file in CSV format")
+@click.option('--by', type=int, default=0, metavar="N",
+              help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
+@click.option('--thresholds', metavar="LIST",
+              help="Depths, e.g. 1,10,30: one more column each, the positions at or above it")
+@click.option('--dist', type=click.File('w'), metavar="FILE",
+              help="Also write the cumulative depth distribution: per contig in header order "
+                   "(or per region, labelled name:start-end), then in total")
+@click.option('--dist-bins', type=int, default=1024, metavar="N",
+              help="Bins of --dist (default 1024); the last one holds every depth at or above N - 1")
+@click.option('--device', type=int, default=0, help="HIP device ordinal")
+@click.option('--decode', type=click.Choice(['gpu', 'host']), default='gpu',
+              help="gpu (default): BGZF inflate and record parse on the device; "
+                   "host: the C++ decoder on host threads")
+@click.option('--legacy-endpos', is_flag=True, default=False,
+              help="Count a mapped read without reference-consuming CIGAR ops on one column "
+                   "(htslib <= 1.9 bam_endpos); default: it adds nothing (current htslib)")
+def coverage(bamfile, outfile, regionfile_blast7, regionfile_csv, by, thresholds, dist, dist_bins, device,
+             decode, legacy_endpos):
+    """
+    Write windowed coverage: mean depth, breadth, depth distribution
+
+    One line `contig start end mean` per window, computed on the GPU: every
+    contig in header order, or the regions of a region file in file order,
+    whole (--by 0) or cut into windows of N positions.  --thresholds adds a
+    header line and, per depth, the positions at or above it.  --dist writes
+    `label depth fraction` lines: the fraction of positions with at least
+    that depth.  Depths are exact: the htslib read cap that `pileup` applies
+    per region query is not applied here.  Single process only.
+    """
+    from . import windows as _windows
+    if regionfile_blast7 and regionfile_csv:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    if by != 0 and by < _windows.MIN_WINDOW:
+        raise click.BadParameter("must be 0 or at least %d (for shorter windows write `depth` runs)"
+                                 % _windows.MIN_WINDOW, param_hint="--by")
+    if thresholds:
+        try:
+            _windows.parse_thresholds(thresholds)
+        except ValueError as e:
+            raise click.BadParameter(str(e), param_hint="--thresholds")
+    if dist_bins < 1:
+        raise click.BadParameter("must be at least 1", param_hint="--dist-bins")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("coverage runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)")
+    if decode == 'gpu':
+        bam = GpuBamFile(bamfile.name, device=device, legacy_endpos=legacy_endpos)
+    else:
+        bam = BamFile(bamfile.name, legacy_endpos=legacy_endpos)
+    log_counts(bam)
+    if dist is not None and dist_bins > _windows.dims()[2]:
+        raise click.BadParameter("at most %d" % _windows.dims()[2], param_hint="--dist-bins")
+    err = None
+    names = [w.split()[0] if w.split() else w for w in bam.references]
+    if regionfile_blast7 or regionfile_csv:
+        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, bam)
+        _, tids, starts, ends, err = resolve_regions(bam, regions)
+        labels = ["%s:%d-%d" % (names[int(t)], a, b) for t, a, b in zip(tids, starts, ends)]
+    else:
+        tids = np.arange(len(bam.lengths), dtype=np.int32)
+        starts = np.zeros(len(tids), np.int64)
+        ends = np.asarray(bam.lengths, np.int64)
+        labels = names
+    n = write_coverage(bam, tids, starts, ends, outfile, device=device, by=by, thresholds=thresholds,
+                       dist=dist, dist_bins=dist_bins, labels=labels)
+    outfile.flush()
+    if dist is not None:
+        dist.flush()
+    log.info("%d windows written", n)
+    if err is not None:      # the regions before a failing one are written first, as depth does
         raise err
 
 

@@ -7,6 +7,8 @@
     eng.depth(tid, start, end)             # int32 numpy
     eng.region_stats(tids, starts, ends)   # structured numpy, exact integers
     eng.depth_runs(tids, starts, ends)     # runs of equal depth (bedGraph form), encoded on the GPU
+    eng.depth_windows(window=500, thresholds="1,10,30")   # per-window sums and threshold counts
+    eng.depth_hist(n_bins=1024)            # depth histogram per segment
     classic_stats(row)                     # -> the dict pileup.classic returns
 
 The statistics formatting here is the host half of the reference's
@@ -131,12 +133,16 @@ class CoverageEngine:
         self.lengths = np.zeros(0, dtype=np.int64)
         self._rcache = None   # the last region arrays passed as-is and their C arguments
         self._runs = None     # the mc_runs handle of depth_runs(), made on first use
+        self._windows = None  # the mc_windows handle of depth_windows() / depth_hist(), likewise
 
     # -- lifecycle
     def close(self):
         if getattr(self, "_runs", None) is not None:
             self._runs.close()
             self._runs = None
+        if getattr(self, "_windows", None) is not None:
+            self._windows.close()
+            self._windows = None
         if getattr(self, "_h", None):
             self._lib.mc_ctx_destroy(self._h)
             self._h = None
@@ -279,6 +285,24 @@ class CoverageEngine:
         Depths are exact (no pileup cap)."""
         from . import runs as _runs
         return _runs.depth_runs(self, tids, starts, ends, quantize)
+
+    def depth_windows(self, tids=None, starts=None, ends=None, window=0, thresholds=None):
+        """The computed depth per window (metacov_amd.windows.WindowCoverage):
+        each segment (as for depth_runs; default: every contig over [0,
+        length)) cut into windows of `window` positions, the last one short;
+        window=0: one window per non-empty segment.  Per window the exact
+        int64 sum of depths and, per threshold, the positions at or above it.
+        thresholds: None, a spec ("1,10,30") or up to 16 strictly increasing
+        non-negative depths.  window is 0 or at least 16."""
+        from . import windows as _windows
+        return _windows.depth_windows(self, tids, starts, ends, window, thresholds)
+
+    def depth_hist(self, tids=None, starts=None, ends=None, n_bins=1024):
+        """int64 [S, n_bins]: per segment (as for depth_runs) the number of
+        positions at each depth; the last bin counts depth >= n_bins - 1.
+        Every row sums to the segment's length."""
+        from . import windows as _windows
+        return _windows.depth_hist(self, tids, starts, ends, n_bins)
 
     def depth_device(self):
         p = ctypes.c_void_p()
