@@ -361,6 +361,134 @@ int mc_windows_timing(const mc_windows* w, float* window_ms, float* combine_ms, 
                       int64_t* tiles);
 int mc_windows_dims(int32_t* tile, int32_t* min_window, int32_t* max_bins, int32_t* hist_groups);
 
+/* ---- per-position base counts (csrc/bases.hip, csrc/bases_src.cpp) ----------
+ * What the reads say at each position: counts of A, C, G, T, N and deletions
+ * (channels MC_BASES_A .. MC_BASES_DEL), the numbers pysam's
+ * AlignmentFile.count_coverage(), samtools mpileup, pysamstats and
+ * bam-readcount report, and the variant sites among them.  Nothing in the
+ * reference (metacov/pileup.py only reads PileupColumn.n); the contract is
+ * this library's own, modelled on count_coverage.  Integer only: results are
+ * exact, identical from call to call and independent of how the reads were
+ * split into batches.  The handle is independent of any mc_ctx; it is not
+ * thread-safe.
+ *
+ * Reads (mc_bases_add_batch; host pointers, copied during the call): n reads
+ * sorted by (tid, pos), the order mc_add_reads demands, also across the
+ * batches of one mc_bases_begin.  Read i has
+ *   tid[i], pos[i]                      0 <= tid < n_ref, pos >= 0
+ *   cigar[cig_off[i] .. cig_off[i+1])   BAM-packed words (len << 4 | op), as
+ *                                       mc_add_reads_cigar
+ *   l_seq[i]                            bases in the read
+ *   seq[seq_off[i] ..]                  nt16 codes, two per byte, high nibble
+ *                                       first ((l_seq + 1) / 2 bytes; any
+ *                                       byte offset), as mc_scan_src_batch
+ *   qual[qual_off[i] ..]                one quality byte per base (l_seq bytes)
+ * cig_off, seq_off and qual_off have n + 1 entries; the last one is the size
+ * of its arena.  Walking a read: from rpos = pos, qpos = 0, per CIGAR op
+ *   M, =, X   each (qpos, rpos) pair counts one into the channel of the base;
+ *             both advance
+ *   D         counts one into DEL at each rpos (no quality test); rpos advances
+ *   N         rpos advances
+ *   I, S      qpos advances
+ *   H, P      (and the unassigned op codes) nothing
+ * nt16 codes 1, 2, 4, 8 are A, C, G, T; every other code, 0 ('=') included,
+ * is N.  With min_baseq > 0 a base whose quality is below it counts nothing,
+ * unless the read's first quality byte is 0xFF (qualities absent), which
+ * passes any threshold.  A batch with an unsorted read, a tid outside
+ * [0, n_ref), a negative pos or l_seq, a CIGAR whose query length (sum of
+ * M/I/S/=/X) differs from l_seq, a reference span above 2^31 - 1 or offsets
+ * outside the arenas is MC_E_INVALID; mc_last_error names the first such
+ * read ("read <i>: ...") and the batch adds nothing.
+ *
+ * Segments (mc_bases_begin) are mc_runs_compute's (tid, start, end): unsorted,
+ * overlapping, duplicated or empty ones are fine, and a segment may run past
+ * the contig's end (the handle knows no contig lengths); a tid outside
+ * [0, n_ref), start < 0, end < start or end > 2^40 is MC_E_INVALID (the
+ * message names the segment).  begin allocates and zeroes counts[6][N],
+ * N = sum of (end - start): plane c, index seg_off[s] + (p - start[s]), is the
+ * count of channel c at position p of segment s (mc_bases_seg_off: S + 1
+ * offsets).  A read counts into every segment that holds the position;
+ * positions no read reaches stay 0.  A second begin starts from zero;
+ * mc_bases_add_batch, _seg_off, _get, _device, _sites and _timing before the
+ * first are MC_E_STATE.  mc_bases_get copies positions [first, first + count)
+ * of the six planes to out[6][count] (MC_E_INVALID outside [0, N]);
+ * mc_bases_device exposes the planes (plane c starts at d_planes + c * stride).
+ *
+ * Device side: a pre-pass kernel per batch (reference span and query length
+ * per read, the checks above, the lowest bad index and the largest span), then
+ * one 512-thread workgroup per tile of at most *tile positions of one segment:
+ * the tile's reads by two binary searches, one LDS integer add per counted
+ * base, and a flush of the LDS planes into the global ones by plain
+ * load-add-store (one owner per tile; batches are ordered on the handle's
+ * stream).  No global atomics.  Counts are uint32.
+ *
+ * Sites (mc_bases_sites), a second stage over the planes on the device: with
+ * depth = A + C + G + T + DEL (N is never an allele), the base allele is the
+ * reference allele where ref (optional, uint8 [N], indexed like a plane:
+ * 0..3 = A/C/G/T, anything else = unknown) gives one, otherwise the allele
+ * with the highest count (ties: the lowest channel); alt is the highest count
+ * among the other four alleles.  Position p is a site iff depth >= min_depth,
+ * alt >= min_count and alt * 10^6 >= min_ppm * depth (64-bit integers;
+ * thresholds >= 0, min_ppm <= 10^6, else MC_E_INVALID).  Segment s owns sites
+ * [site_first[s], site_first[s + 1]); site i is at site_pos[i] (relative to
+ * the contig, ascending within a segment) with the six counts
+ * site_counts[i][0..5].  Results stay in device memory owned by the handle
+ * (buffers only grow) until the next mc_bases_sites, _add_batch or _begin.
+ * mc_bases_timing: HIP-event times since begin of the pre-pass and pileup
+ * kernels (summed over the batches) and of the last sites call, the tile
+ * count and the reads added.  mc_bases_dims (test hook): the tile size.
+ *
+ * mc_bases_src_*: the host record source that stands in for the read loop of
+ * count_coverage (htslib sam_itr_next, bam_get_cigar / bam_get_seq /
+ * bam_get_qual): the kept records of a coordinate-sorted BAM in the layout
+ * above (each read's bases start on a 4-byte boundary).  Kept: tid >= 0,
+ * (flag & flag_filter) == 0 (0x704: pysam's read_callback='all' and this
+ * library's pileup filter) and mapq >= min_mapq.  Kept records without SEQ and
+ * kept records whose CIGAR query length (CG:B,I resolved as htslib's
+ * bam_read1 does) differs from l_seq are skipped and counted
+ * (mc_bases_src_counts).  An unsorted file is MC_E_INVALID.  mc_bases_src_next
+ * hands out up to max_reads reads (it stops once max_bases bases are in);
+ * *n == 0 at the end of the file.  mc_bases_src_batch: the arrays of the last
+ * batch, valid until the next call on the source. */
+#define MC_BASES_A   0
+#define MC_BASES_C   1
+#define MC_BASES_G   2
+#define MC_BASES_T   3
+#define MC_BASES_N   4
+#define MC_BASES_DEL 5
+typedef struct mc_bases mc_bases;
+int mc_bases_create(int device, int32_t n_ref, mc_bases** out);
+int mc_bases_destroy(mc_bases* h);
+int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const int64_t* start, const int64_t* end,
+                   int32_t min_baseq);
+int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                       const int64_t* cig_off /* n + 1 */, const uint32_t* cigar, const int32_t* l_seq,
+                       const int64_t* seq_off /* n + 1 */, const uint8_t* seq,
+                       const int64_t* qual_off /* n + 1 */, const uint8_t* qual);
+int mc_bases_seg_off(const mc_bases* h, int64_t* seg_off /* S + 1 */);
+int mc_bases_get(const mc_bases* h, int64_t first, int64_t count, uint32_t* out /* 6 x count */);
+int mc_bases_device(const mc_bases* h, const uint32_t** d_planes, int64_t* stride, int64_t* n);
+int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                   const uint8_t* ref /* N, or NULL */, int64_t* n_sites);
+int mc_bases_sites_first(const mc_bases* h, int64_t* site_first /* S + 1 */);
+int mc_bases_sites_get(const mc_bases* h, int64_t first, int64_t count, int64_t* site_pos /* count */,
+                       uint32_t* site_counts /* count x 6 */);
+int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pileup_ms, float* sites_ms, int64_t* tiles,
+                    int64_t* reads);
+int mc_bases_dims(int32_t* tile);
+
+typedef struct mc_bases_src mc_bases_src;
+int mc_bases_src_open(const char* path, int n_threads, uint32_t flag_filter, int min_mapq, mc_bases_src** out);
+int mc_bases_src_close(mc_bases_src* s);
+int mc_bases_src_n_targets(const mc_bases_src* s, int32_t* n);
+int mc_bases_src_target(const mc_bases_src* s, int32_t i, const char** name, int64_t* length);
+int mc_bases_src_next(mc_bases_src* s, int64_t max_reads, int64_t max_bases, int64_t* n);
+int mc_bases_src_batch(const mc_bases_src* s, const int32_t** tid, const int32_t** pos, const int64_t** cig_off,
+                       const uint32_t** cigar, const int32_t** l_seq, const int64_t** seq_off,
+                       const uint8_t** seq, const int64_t** qual_off, const uint8_t** qual);
+int mc_bases_src_counts(const mc_bases_src* s, int64_t* records, int64_t* kept, int64_t* no_seq,
+                        int64_t* bad_cigar);
+
 /* ---- htslib's pileup read cap (opt-in) -----------------------------------
  * pysam's AlignmentFile.pileup(ref, start, end) (pileup.py:13) runs htslib's
  * pileup with max_depth = 8000: bam_plp_push drops a read that starts where

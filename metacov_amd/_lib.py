@@ -137,6 +137,27 @@ SIGNATURES = {
     "mc_windows_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                           ctypes.POINTER(ctypes.c_float), _PI64],
     "mc_windows_dims": [_PI32, _PI32, _PI32, _PI32],
+    # per-position base counts (csrc/bases.hip, csrc/bases_src.cpp)
+    "mc_bases_create": [ctypes.c_int, _I32, _PP],
+    "mc_bases_destroy": [_P],
+    "mc_bases_begin": [_P, _I64, _P, _P, _P, _I32],
+    "mc_bases_add_batch": [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mc_bases_seg_off": [_P, _P],
+    "mc_bases_get": [_P, _I64, _I64, _P],
+    "mc_bases_device": [_P, _PP, _PI64, _PI64],
+    "mc_bases_sites": [_P, _I64, _I64, _I64, _P, _PI64],
+    "mc_bases_sites_first": [_P, _P],
+    "mc_bases_sites_get": [_P, _I64, _I64, _P, _P],
+    "mc_bases_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                        ctypes.POINTER(ctypes.c_float), _PI64, _PI64],
+    "mc_bases_dims": [_PI32],
+    "mc_bases_src_open": [ctypes.c_char_p, ctypes.c_int, _U32, ctypes.c_int, _PP],
+    "mc_bases_src_close": [_P],
+    "mc_bases_src_n_targets": [_P, _PI32],
+    "mc_bases_src_target": [_P, _I32, ctypes.POINTER(ctypes.c_char_p), _PI64],
+    "mc_bases_src_next": [_P, _I64, _I64, _PI64],
+    "mc_bases_src_batch": [_P, _PP, _PP, _PP, _PP, _PP, _PP, _PP, _PP, _PP],
+    "mc_bases_src_counts": [_P, _PI64, _PI64, _PI64, _PI64],
     "mc_depth_cap_mask": [_I64, _P, _P, _P, _I32, ctypes.c_int, _P, _PI64],
     "mc_depth_cap_mask_device": [ctypes.c_int, _I64, _P, _P, _P, _I32, _P, _PI64],
     "mc_add_reads_capped": [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _I32, _PI64],

@@ -1,0 +1,292 @@
+"""Per-position base counts: what the reads say at each position.
+
+    with BaseCounter(n_ref) as bc:
+        bc.begin(tids, starts, ends, min_baseq=15)
+        bc.add_bam("x.bam")                  # or add_reads(...) batch by batch
+        planes = bc.counts()                 # uint32 [6, N]: A, C, G, T, N, DEL
+        sites = bc.sites(min_depth=10, min_count=2, min_ppm=10000)
+
+    a, c, g, t = count_coverage("x.bam", "contig_1", 0, 1000)
+
+The pileup runs on the GPU (csrc/bases.hip, mc_bases_* in
+include/metacov_amd.h); the records come from the host source in
+csrc/bases_src.cpp, so file decode, not the kernel, bounds the path end to
+end.  These are the numbers of pysam's `AlignmentFile.count_coverage()`,
+`samtools mpileup`, pysamstats and bam-readcount; the reference has no
+counterpart.  The contract (CIGAR walk, channels, quality rule, segments,
+sites) is the header's.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, ptr
+
+CHANNELS = ("A", "C", "G", "T", "N", "DEL")
+A, C, G, T, N, DEL = range(6)
+FLAG_FILTER = 0x704
+GET_CHUNK = 1 << 22                 # positions per mc_bases_get of write_all
+
+
+def dims(lib=None):
+    """Tile positions of the pileup kernel."""
+    lib = lib or _lib.load()
+    t = ctypes.c_int32()
+    check(lib.mc_bases_dims(ctypes.byref(t)), lib)
+    return t.value
+
+
+class Sites:
+    """Sites of S segments, in segment order: segment s owns rows
+    first[s] .. first[s + 1]; pos [n] int64 relative to the contig, ascending
+    within a segment; counts [n, 6] uint32 (A, C, G, T, N, DEL)."""
+
+    def __init__(self, first, pos, counts):
+        self.first = np.asarray(first, np.int64)
+        self.pos = np.asarray(pos, np.int64)
+        self.counts = np.asarray(counts, np.uint32).reshape(-1, 6)
+
+    def __len__(self):
+        return len(self.pos)
+
+
+class BaseSource:
+    """One mc_bases_src: the kept records of a coordinate-sorted BAM."""
+
+    def __init__(self, path, n_threads=0, flag_filter=FLAG_FILTER, min_mapq=0, lib=None):
+        self._lib = lib or _lib.load()
+        self._h = ctypes.c_void_p()
+        check(self._lib.mc_bases_src_open(str(path).encode(), int(n_threads), int(flag_filter), int(min_mapq),
+                                          ctypes.byref(self._h)), self._lib)
+        n = ctypes.c_int32()
+        check(self._lib.mc_bases_src_n_targets(self._h, ctypes.byref(n)), self._lib)
+        self.references, self.lengths = [], []
+        for i in range(n.value):
+            name, length = ctypes.c_char_p(), ctypes.c_int64()
+            check(self._lib.mc_bases_src_target(self._h, i, ctypes.byref(name), ctypes.byref(length)), self._lib)
+            self.references.append(name.value.decode())
+            self.lengths.append(length.value)
+
+    def next(self, max_reads=1 << 20, max_bases=1 << 27):
+        """The next batch as a dict of numpy views (valid until the next call),
+        in mc_bases_add_batch's layout; None at the end of the file."""
+        n = ctypes.c_int64()
+        check(self._lib.mc_bases_src_next(self._h, int(max_reads), int(max_bases), ctypes.byref(n)), self._lib)
+        n = n.value
+        if n == 0:
+            return None
+        p = [ctypes.c_void_p() for _ in range(9)]
+        check(self._lib.mc_bases_src_batch(self._h, *[ctypes.byref(x) for x in p]), self._lib)
+
+        def view(q, dtype, count):
+            if count == 0:
+                return np.zeros(0, dtype)
+            buf = (ctypes.c_char * (count * np.dtype(dtype).itemsize)).from_address(q.value)
+            return np.frombuffer(buf, dtype=dtype, count=count)
+
+        cig_off = view(p[2], np.int64, n + 1)
+        seq_off = view(p[5], np.int64, n + 1)
+        qual_off = view(p[7], np.int64, n + 1)
+        return {"tid": view(p[0], np.int32, n), "pos": view(p[1], np.int32, n), "cig_off": cig_off,
+                "cigar": view(p[3], np.uint32, int(cig_off[n])), "l_seq": view(p[4], np.int32, n),
+                "seq_off": seq_off, "seq": view(p[6], np.uint8, int(seq_off[n])),
+                "qual_off": qual_off, "qual": view(p[8], np.uint8, int(qual_off[n]))}
+
+    def counts(self):
+        """Records read so far: total, kept (past the filters), and the kept
+        ones skipped for no SEQ or for a CIGAR whose query length differs from
+        l_seq."""
+        v = [ctypes.c_int64() for _ in range(4)]
+        check(self._lib.mc_bases_src_counts(self._h, *[ctypes.byref(x) for x in v]), self._lib)
+        return dict(zip(("records", "kept", "no_seq", "bad_cigar"), (x.value for x in v)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mc_bases_src_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class BaseCounter:
+    """One mc_bases (device buffers that only grow, reused between begins)."""
+
+    def __init__(self, n_ref, device=0, lib=None):
+        self._lib = lib or _lib.load()
+        self._h = ctypes.c_void_p()
+        self.n_ref = int(n_ref)
+        self.device = int(device)
+        self._S = 0
+        check(self._lib.mc_bases_create(self.device, self.n_ref, ctypes.byref(self._h)), self._lib)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mc_bases_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def begin(self, tids, starts, ends, min_baseq=0):
+        """Allocates and zeroes the planes of the segments [start, end) of
+        contig tid; returns N, the positions in all."""
+        tids = np.ascontiguousarray(tids, dtype=np.int32)
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        ends = np.ascontiguousarray(ends, dtype=np.int64)
+        if not len(tids) == len(starts) == len(ends):
+            raise ValueError("tids / starts / ends lengths differ")
+        check(self._lib.mc_bases_begin(self._h, len(tids), ptr(tids), ptr(starts), ptr(ends), int(min_baseq)),
+              self._lib)
+        self._S = len(tids)
+        return int(self.seg_off[-1])
+
+    def add_reads(self, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual):
+        """One batch of reads sorted by (tid, pos) (mc_bases_add_batch)."""
+        tid = np.ascontiguousarray(tid, dtype=np.int32)
+        n = len(tid)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        l_seq = np.ascontiguousarray(l_seq, dtype=np.int32)
+        cig_off, seq_off, qual_off = (np.ascontiguousarray(a, dtype=np.int64) for a in (cig_off, seq_off, qual_off))
+        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8)
+        if len(pos) != n or len(l_seq) != n or any(len(a) != n + 1 for a in (cig_off, seq_off, qual_off)):
+            raise ValueError("read arrays of inconsistent length")
+        if n and (cig_off[n] > len(cigar) or seq_off[n] > len(seq) or qual_off[n] > len(qual)):
+            raise ValueError("the last offset exceeds its arena")
+        check(self._lib.mc_bases_add_batch(self._h, n, ptr(tid), ptr(pos), ptr(cig_off), ptr(cigar), ptr(l_seq),
+                                           ptr(seq_off), ptr(seq), ptr(qual_off), ptr(qual)), self._lib)
+
+    def add_bam(self, path, flag_filter=FLAG_FILTER, min_mapq=0, max_reads=1 << 20, max_bases=1 << 27,
+                n_threads=0):
+        """Every kept record of a coordinate-sorted BAM, batch by batch;
+        returns the source's record counts."""
+        with BaseSource(path, n_threads, flag_filter, min_mapq, self._lib) as src:
+            while True:
+                b = src.next(max_reads, max_bases)
+                if b is None:
+                    break
+                self.add_reads(b["tid"], b["pos"], b["cig_off"], b["cigar"], b["l_seq"], b["seq_off"], b["seq"],
+                               b["qual_off"], b["qual"])
+            return src.counts()
+
+    @property
+    def seg_off(self):
+        """int64 [S + 1]: segment s owns plane indices seg_off[s] .. seg_off[s + 1]."""
+        out = np.zeros(self._S + 1, np.int64)
+        check(self._lib.mc_bases_seg_off(self._h, ptr(out)), self._lib)
+        return out
+
+    def counts(self, first=0, count=None):
+        """uint32 [6, count]: the planes A, C, G, T, N, DEL over plane indices
+        first .. first + count (default: all N)."""
+        if count is None:
+            count = int(self.seg_off[-1]) - int(first)
+        out = np.zeros((6, max(int(count), 0)), np.uint32)
+        check(self._lib.mc_bases_get(self._h, int(first), int(count), ptr(out)), self._lib)
+        return out
+
+    def sites(self, min_depth=1, min_count=1, min_ppm=0, ref=None):
+        """The sites among the positions (see the header); ref: optional uint8
+        [N], indexed like a plane, 0..3 = A/C/G/T, anything else unknown."""
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, dtype=np.uint8)
+            if len(ref) != int(self.seg_off[-1]):
+                raise ValueError("the reference plane must have one entry per position")
+        n = ctypes.c_int64()
+        check(self._lib.mc_bases_sites(self._h, int(min_depth), int(min_count), int(min_ppm), ptr(ref),
+                                       ctypes.byref(n)), self._lib)
+        n = n.value
+        first = np.zeros(self._S + 1, np.int64)
+        check(self._lib.mc_bases_sites_first(self._h, ptr(first)), self._lib)
+        pos = np.zeros(n, np.int64)
+        cnt = np.zeros((n, 6), np.uint32)
+        check(self._lib.mc_bases_sites_get(self._h, 0, n, ptr(pos), ptr(cnt)), self._lib)
+        return Sites(first, pos, cnt)
+
+    def timing(self):
+        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        t, r = ctypes.c_int64(), ctypes.c_int64()
+        check(self._lib.mc_bases_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(t),
+                                        ctypes.byref(r)), self._lib)
+        return {"prepass_ms": a.value, "pileup_ms": b.value, "sites_ms": c.value, "tiles": t.value,
+                "reads": r.value}
+
+
+def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, min_mapq=0, device=0):
+    """pysam's AlignmentFile.count_coverage(contig, start, stop,
+    quality_threshold) with read_callback='all': four uint32 arrays A, C, G, T
+    of stop - start counts (default: the whole contig)."""
+    lib = _lib.load()
+    with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
+        names = [w.split()[0] if w.split() else w for w in src.references]
+        if contig not in names:
+            raise KeyError("contig '%s' is not in the header of %s" % (contig, path))
+        tid = names.index(contig)
+        length = src.lengths[tid]
+    start = 0 if start is None else int(start)
+    stop = length if stop is None else int(stop)
+    if start < 0 or stop < start:
+        raise ValueError("bad range [%d, %d)" % (start, stop))
+    with BaseCounter(len(names), device, lib) as bc:
+        bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
+        bc.add_bam(path, min_mapq=min_mapq)
+        planes = bc.counts()
+    return planes[A].copy(), planes[C].copy(), planes[G].copy(), planes[T].copy()
+
+
+# ------------------------------------------------------------------ output
+
+HEADER = "contig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tDEL\n"
+_REF_CODE = np.full(256, 4, np.uint8)
+for _i, _ch in enumerate("ACGT"):
+    _REF_CODE[ord(_ch)] = _REF_CODE[ord(_ch.lower())] = _i
+
+
+def ref_codes(letters):
+    """uint8 ASCII letters -> the reference plane's codes (0..3, 4 = other)."""
+    return _REF_CODE[np.asarray(letters, np.uint8)]
+
+
+def write_sites(fh, name, pos, counts, ref=None):
+    """Tab-separated `contig pos ref depth A C G T N DEL` lines of one contig:
+    pos [n] 0-based positions (written 1-based, as mpileup and VCF), counts
+    [n, 6], ref [n] uint8 ASCII letters or None ('.').  depth = A + C + G + T
+    + DEL.  Returns the lines written."""
+    pos = np.asarray(pos, np.int64)
+    n = len(pos)
+    if n == 0:
+        return 0
+    counts = np.asarray(counts).reshape(n, 6).astype(np.int64)
+    depth = counts[:, [A, C, G, T, DEL]].sum(axis=1)
+    if ref is None:
+        letters = np.full(n, ".", dtype="U1")
+    else:
+        letters = np.char.upper(np.asarray(ref, np.uint8).view("S1").astype("U1"))
+    line = np.char.add(str(name) + "\t", (pos + 1).astype(str))
+    line = np.char.add(np.char.add(line, "\t"), letters)
+    for col in [depth] + [counts[:, c] for c in range(6)]:
+        line = np.char.add(np.char.add(line, "\t"), col.astype(str))
+    fh.write("\n".join(line.tolist()))
+    fh.write("\n")
+    return n

@@ -32,6 +32,15 @@ writes the mean depth per contig, region or fixed window, the positions at or
 above each threshold, and the cumulative depth distribution, all reduced on
 the GPU (metacov_amd/windows.py); one process, no read cap.
 
+Base counts (no counterpart in the reference either):
+
+    python -m metacov_amd.cli bases -b X.bam [-o out.tsv] [-f ref.fa] [-rc R.csv | -rb R.blast7] [--min-baseq 0]
+                                    [--min-mapq 0] [--min-depth 1] [--min-count 1] [--min-frac 0.0] [--all]
+
+writes `contig pos ref depth A C G T N DEL` for the variant sites, or with
+`--all` for every position, counted on the GPU (metacov_amd/bases.py); one
+process, no read cap, `pos` 1-based.
+
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
     python -m torch.distributed.run --nproc-per-node 8 -m metacov_amd.cli pileup -b X.bam ...
@@ -711,6 +720,135 @@ def coverage(bamfile, outfile, regionfile_blast7, regionfile_csv, by, thresholds
         dist.flush()
     log.info("%d windows written", n)
     if err is not None:      # the regions before a failing one are written first, as depth does
+        raise err
+
+
+BASES_GROUP_POSITIONS = 1 << 30     # positions per mc_bases_begin of `bases` (24 B each on the device)
+
+
+def _segment_letters(fa, name, start, end):
+    """uint8 ASCII reference letters of [start, end) of contig `name`; 'N'
+    where the FASTA has no base (unknown contig, past its end)."""
+    out = np.full(int(end - start), ord("N"), np.uint8)
+    try:
+        off, n = fa.span(name, int(start), int(end))
+    except KeyError:
+        return out
+    lead = min(max(int(start), 0), int(end)) - int(start)      # (start >= 0 here: always 0)
+    out[lead:lead + n] = fa.buffer[off:off + n]
+    return out
+
+
+def write_bases(path, references, tids, starts, ends, outfile, fasta=None, device=0, min_baseq=0, min_mapq=0,
+                min_depth=1, min_count=1, min_ppm=0, every=False):
+    """The base-count table of the segments (header contig ids), group by
+    group (each group is one pass over the BAM), each written before the next
+    is computed.  Returns (lines written, the source's record counts)."""
+    from . import bases as _bases
+    names = [w.split()[0] if w.split() else w for w in references]
+    outfile.write(_bases.HEADER)
+    written, counts = 0, None
+    if len(tids) == 0:
+        return 0, None
+    fa = _experimental.FastaFile(fasta) if fasta else None
+    with _bases.BaseCounter(len(references), device) as bc:
+        for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
+            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
+            counts = bc.add_bam(path, min_mapq=min_mapq)
+            seg_off = bc.seg_off
+            letters = None
+            if fa is not None:
+                letters = np.concatenate([_segment_letters(fa, names[int(tids[i])], starts[i], ends[i])
+                                          for i in range(a, b)] + [np.zeros(0, np.uint8)])
+            if every:
+                for i in range(a, b):
+                    o, n = int(seg_off[i - a]), int(ends[i] - starts[i])
+                    for c0 in range(0, n, _bases.GET_CHUNK):
+                        c1 = min(n, c0 + _bases.GET_CHUNK)
+                        planes = bc.counts(o + c0, c1 - c0)
+                        written += _bases.write_sites(
+                            outfile, names[int(tids[i])], np.arange(starts[i] + c0, starts[i] + c1), planes.T,
+                            None if letters is None else letters[o + c0:o + c1])
+            else:
+                s = bc.sites(min_depth, min_count, min_ppm,
+                             ref=None if letters is None else _bases.ref_codes(letters))
+                for i in range(a, b):
+                    r0, r1 = int(s.first[i - a]), int(s.first[i - a + 1])
+                    idx = int(seg_off[i - a]) + (s.pos[r0:r1] - int(starts[i]))
+                    written += _bases.write_sites(outfile, names[int(tids[i])], s.pos[r0:r1], s.counts[r0:r1],
+                                                  None if letters is None else letters[idx])
+    return written, counts
+
+
+@main.command()
+@click.option('--bamfile', '-b', type=click.File('rb'), required=True,
+              help="Input BAM file. Must be coordinate-sorted.")
+@click.option('--outfile', '-o', type=click.File('w'), default="-",
+              help="Output table (default STDOUT)")
+@click.option('--reference-fasta', '-f', type=click.File('rb'),
+              help="Reference FASTA (plain or gzip): fills the ref column and makes the reference base "
+                   "the base allele")
+@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
+              help="Input Region file in BLAST7 format")
+@click.option('--regionfile-csv', '-rc', type=click.File('r'),
+              help="Input Region file in CSV format")
+@click.option('--min-baseq', type=click.IntRange(0), default=0,
+              help="Count only bases of at least this quality (deletions always count)")
+@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
+              help="Use only reads of at least this mapping quality")
+@click.option('--min-depth', type=click.IntRange(0), default=1,
+              help="A site needs A + C + G + T + DEL of at least this")
+@click.option('--min-count', type=click.IntRange(0), default=1,
+              help="A site needs this many reads on its strongest non-base allele")
+@click.option('--min-frac', type=float, default=0.0,
+              help="A site needs this fraction (0..1) of its depth on that allele")
+@click.option('--all', 'every', is_flag=True, default=False,
+              help="Write every position of the regions, not only the sites")
+@click.option('--device', type=int, default=0, help="HIP device ordinal")
+def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, min_baseq, min_mapq, min_depth,
+          min_count, min_frac, every, device):
+    """
+    Write per-position base counts and variant sites
+
+    One line `contig pos ref depth A C G T N DEL` per site: a position whose
+    strongest allele besides the base allele (the reference base with -f,
+    else the most frequent allele) passes --min-count and --min-frac at a
+    depth of at least --min-depth; with --all every position of the regions.
+    pos is 1-based, as in mpileup and VCF; ref is `.` without -f.  Every
+    contig in header order, or the regions of a region file in file order.
+    Counted on the GPU; single process only.
+    """
+    from . import bases as _bases
+    if regionfile_blast7 and regionfile_csv:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
+        raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
+    min_ppm = int(round(min_frac * 1e6))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("bases runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)")
+    # (read by experimental.FastaFile as `pileup -f -k` and `scan -f` read theirs: plain or gzip.  `pileup`
+    # also fails where pysam's faidx would, to match the reference; `bases` has no reference to match)
+    fasta = reference_fasta.name if reference_fasta else None
+    with _bases.BaseSource(bamfile.name) as head:
+        references, lengths = list(head.references), list(head.lengths)
+    err = None
+    if regionfile_blast7 or regionfile_csv:
+        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
+        _, tids, starts, ends, err = resolve_regions(head, regions)
+    else:
+        tids = np.arange(len(lengths), dtype=np.int32)
+        starts = np.zeros(len(tids), np.int64)
+        ends = np.asarray(lengths, np.int64)
+    n, counts = write_bases(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
+                            min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth, min_count=min_count,
+                            min_ppm=min_ppm, every=every)
+    outfile.flush()
+    if counts:
+        log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
+                 "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    log.info("%d lines written", n)
+    if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err
 
 

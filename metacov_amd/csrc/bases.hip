@@ -1,0 +1,823 @@
+// Per-position base counts: what the reads say at each position (A, C, G, T,
+// N, deletion), the form pysam's AlignmentFile.count_coverage(), samtools
+// mpileup, pysamstats and bam-readcount report (nothing in the reference,
+// whose pileup only reads PileupColumn.n), and the variant sites among them.
+//
+// The contract (include/metacov_amd.h, "per-position base counts") in short:
+// every read walks its CIGAR from pos with qpos = 0; M/=/X count the base at
+// (qpos, rpos) into its channel, D counts DEL, N advances the reference, I/S
+// the query, H/P nothing.  nt16 codes 1/2/4/8 are A/C/G/T, every other code
+// is N.  A base below min_baseq counts nothing unless the read's qualities
+// are absent (first byte 0xFF); DEL takes no quality test.  The planes are
+// counts[6][N] over the concatenated segments of mc_bases_begin.
+//
+// Launches, all on the handle's stream, none waiting on another workgroup:
+//   bases_prepass_kernel  one thread per read of a batch: reference span and
+//                         query length of its CIGAR, the validity checks
+//                         (order against the predecessor as one 64-bit
+//                         compare), the lowest bad index through an atomic
+//                         min and the batch's largest span through an atomic
+//                         max per wave.  The host reads those two words.
+//   bases_pileup_kernel   one 512-thread workgroup per tile of at most kTile
+//                         positions of one segment; only the tiles between
+//                         the batch's first and last read in (tid, position)
+//                         order are launched.  Two binary searches in the
+//                         sorted batch give the reads of the tile's
+//                         contig with pos in [tile start - max span, tile
+//                         end); a tile with none returns before touching LDS
+//                         or HBM.  Waves take the reads 64 at a time: lane i
+//                         loads read i's words, then the reads that reach
+//                         the tile are walked in turn with those words
+//                         broadcast; the CIGAR op loop is wave-uniform
+//                         (scalar loads of further ops); lanes stride over
+//                         the op's positions clipped to the tile; one
+//                         LDS integer add per counted base into 6 planes x
+//                         kTile x 4 B = 48 KiB.  The flush adds the LDS
+//                         planes into the global ones, 16 bytes per lane,
+//                         with plain load-add-store: a tile has one owner in
+//                         a launch and the launches of successive batches
+//                         are ordered on the stream.  No global atomics.
+//   sites_count / scan / emit   the count - scan - emit pattern of runs.hip
+//                         over the planes with the site predicate; the host
+//                         reads the total (8 bytes) between scan and emit.
+//
+// A tile whose first plane index is not 16-byte aligned starts `lead` (1..3)
+// elements into its LDS window and holds at most kTile - lead positions, so
+// LDS element k always pairs with plane element out - lead + k and the
+// 16-byte flush is aligned; window elements outside the tile are never
+// counted into and never written.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "../../include/metacov_amd.h"
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 512;
+constexpr int kWaves = kThreads / 64;
+constexpr int kTile = 2048;                         // positions per tile: 6 x 4 B x 2048 = 48 KiB of LDS
+constexpr int kPlanes = 6;                          // A, C, G, T, N, DEL
+constexpr int kRounds = kTile / kThreads;           // positions per thread of the sites kernels
+constexpr int kScanThreads = 1024;
+constexpr int kScanWidth = kScanThreads * 4;        // tiles per iteration of the scan
+constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_runs_compute's bound
+constexpr unsigned long long kNoBad = ~0ull;
+constexpr uint32_t kQueryOps = 0x193u;              // M I S = X advance the query
+constexpr uint32_t kRefOps = 0x18Du;                // M D N = X advance the reference
+
+struct Tile {
+    int64_t out;       // plane index of the tile's first position
+    int64_t rel;       // contig-relative position of it
+    int32_t n;         // positions (lead + n <= kTile)
+    int32_t tid;
+    int32_t seg;
+    int32_t lead;      // out & 3: elements of the aligned window in front of it
+};
+static_assert(sizeof(Tile) == 32, "tile table entry");
+
+// One batch of reads in device memory (the layout of mc_bases_add_batch).
+struct Batch {
+    const int32_t* tid;
+    const int32_t* pos;
+    const int32_t* l_seq;
+    const int64_t* cig_off;
+    const uint32_t* cigar;
+    const int64_t* seq_off;
+    const uint8_t* seq;
+    const int64_t* qual_off;
+    const uint8_t* qual;
+    int64_t n, n_words, seq_bytes, qual_bytes;
+};
+
+struct SiteArgs {
+    unsigned long long min_depth, min_count, min_ppm;
+};
+
+__device__ __forceinline__ long long read_key(int32_t tid, int32_t pos) {
+    return (long long)(((unsigned long long)(uint32_t)tid << 32) | (uint32_t)pos);
+}
+
+__global__ __launch_bounds__(kThreads) void bases_prepass_kernel(Batch b, int32_t n_ref,
+                                                                int32_t* __restrict__ span,
+                                                                unsigned long long* __restrict__ bad,
+                                                                int32_t* __restrict__ max_span) {
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    int32_t sp = 0;
+    if (i < b.n) {
+        const int32_t tid = b.tid[i], pos = b.pos[i], l = b.l_seq[i];
+        const int64_t c0 = b.cig_off[i], c1 = b.cig_off[i + 1];
+        const int64_t so = b.seq_off[i], qo = b.qual_off[i];
+        bool ok = tid >= 0 && tid < n_ref && pos >= 0 && l >= 0 && c0 >= 0 && c1 >= c0 && c1 <= b.n_words;
+        ok = ok && so >= 0 && so + ((int64_t)l + 1) / 2 <= b.seq_bytes && qo >= 0 && qo + l <= b.qual_bytes;
+        if (ok && i > 0) ok = read_key(b.tid[i - 1], b.pos[i - 1]) <= read_key(tid, pos);
+        if (ok) {
+            int64_t q = 0, r = 0;
+            for (int64_t k = c0; k < c1; ++k) {
+                const uint32_t cw = b.cigar[k];
+                const uint32_t op = cw & 15u;
+                if ((kQueryOps >> op) & 1u) q += cw >> 4;
+                if ((kRefOps >> op) & 1u) r += cw >> 4;
+            }
+            ok = q == l && r <= INT32_MAX;
+            if (ok) sp = (int32_t)r;
+        }
+        span[i] = sp;
+        if (!ok) atomicMin(bad, (unsigned long long)i);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sp = max(sp, __shfl_xor(sp, off, 64));
+    // (the plain look first: after the first waves nearly every wave's maximum is already there, and
+    // same-address atomics serialise)
+    if ((threadIdx.x & 63) == 0 && sp > __atomic_load_n(max_span, __ATOMIC_RELAXED)) atomicMax(max_span, sp);
+}
+
+// Lane i's value, wave-uniform (i is wave-uniform).
+__device__ __forceinline__ int32_t bcast(int32_t v, int i) { return __builtin_amdgcn_readlane(v, i); }
+__device__ __forceinline__ int64_t bcast64(int64_t v, int i) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)v, i);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)((uint64_t)v >> 32), i);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// First read at or after (tid, pos) in the sorted batch; at most 64 steps.
+__device__ __forceinline__ int64_t lower_bound(const Batch& b, int32_t tid, int64_t pos) {
+    int64_t a = 0, z = b.n;
+    while (a < z) {
+        const int64_t m = a + ((z - a) >> 1);
+        const int32_t mt = b.tid[m];
+        if (mt < tid || (mt == tid && (int64_t)b.pos[m] < pos))
+            a = m + 1;
+        else
+            z = m;
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(kThreads) void bases_pileup_kernel(Batch b, const int32_t* __restrict__ span,
+                                                               const Tile* __restrict__ tiles,
+                                                               const int32_t* __restrict__ order, int32_t max_span,
+                                                               int32_t min_baseq, uint32_t* __restrict__ planes,
+                                                               int64_t stride) {
+    __shared__ __attribute__((aligned(16))) uint32_t acc[kPlanes * kTile];
+    const Tile t = tiles[order[blockIdx.x]];
+    const int64_t t0 = t.rel, t1 = t.rel + t.n;
+    const int64_t lo = lower_bound(b, t.tid, t0 > max_span ? t0 - max_span : 0);
+    const int64_t hi = lower_bound(b, t.tid, t1);
+    if (lo >= hi) return;
+    for (int k = threadIdx.x * 4; k < kPlanes * kTile; k += kThreads * 4)
+        *reinterpret_cast<uint4*>(&acc[k]) = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    // A wave takes 64 consecutive reads at a time: lane i loads read i's words (coalesced, independent
+    // loads), then the reads that reach the tile are walked one by one with those words broadcast.
+    for (int64_t g = lo + 64 * (int64_t)wave; g < hi; g += 64 * kWaves) {
+        const int64_t mine = g + lane;
+        const bool have = mine < hi;
+        const int32_t m_pos = have ? b.pos[mine] : 0;
+        const int32_t m_span = have ? span[mine] : 0;
+        const int32_t m_l = have ? b.l_seq[mine] : 0;
+        const int64_t m_c0 = have ? b.cig_off[mine] : 0, m_c1 = have ? b.cig_off[mine + 1] : 0;
+        const int64_t m_so = have ? b.seq_off[mine] : 0, m_qo = have ? b.qual_off[mine] : 0;
+        const uint32_t m_cw = m_c1 > m_c0 ? b.cigar[m_c0] : 0u;        // the first op: the only one of most reads
+        const int32_t m_q0 = m_l > 0 ? (int32_t)b.qual[m_qo] : 0;
+        unsigned long long todo = __ballot(have && (int64_t)m_pos + m_span > t0);
+        while (todo) {
+            const int i = __ffsll(todo) - 1;
+            todo &= todo - 1;
+            const int64_t pos = bcast(m_pos, i), l = bcast(m_l, i);
+            const int64_t c0 = bcast64(m_c0, i), c1 = bcast64(m_c1, i);
+            const int64_t so = bcast64(m_so, i), qo = bcast64(m_qo, i);
+            const bool test_q = min_baseq > 0 && !(l > 0 && bcast(m_q0, i) == 0xFF);
+            int64_t rp = pos, q = 0;
+            for (int64_t k = c0; k < c1 && rp < t1; ++k) {
+                const uint32_t cw = k == c0 ? (uint32_t)bcast((int32_t)m_cw, i) : b.cigar[k];
+                const uint32_t op = cw & 15u;
+                const int64_t len = cw >> 4;
+                if (op == 0 || op == 7 || op == 8) {
+                    const int64_t e = rp + len < t1 ? rp + len : t1;
+                    for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64) {
+                        const int64_t qq = q + (j - rp);
+                        if (qq < l) {
+                            const uint32_t byte = b.seq[so + (qq >> 1)];
+                            const uint32_t code = (qq & 1) ? (byte & 15u) : (byte >> 4);
+                            if (!test_q || (int32_t)b.qual[qo + qq] >= min_baseq) {
+                                const int ch = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : 4;
+                                atomicAdd(&acc[ch * kTile + t.lead + (int)(j - t0)], 1u);
+                            }
+                        }
+                    }
+                    rp += len;
+                    q += len;
+                } else if (op == 2) {
+                    const int64_t e = rp + len < t1 ? rp + len : t1;
+                    for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64)
+                        atomicAdd(&acc[5 * kTile + t.lead + (int)(j - t0)], 1u);
+                    rp += len;
+                } else if (op == 3) {
+                    rp += len;
+                } else if (op == 1 || op == 4) {
+                    q += len;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int first = t.lead, last = t.lead + t.n;          // the tile's part of the window
+#pragma unroll
+    for (int c = 0; c < kPlanes; ++c) {
+        uint32_t* g = planes + c * stride + (t.out - t.lead);   // 16-byte aligned
+        for (int k = threadIdx.x * 4; k < kTile; k += kThreads * 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(&acc[c * kTile + k]);
+            if (!(v.x | v.y | v.z | v.w)) continue;
+            if (k >= first && k + 4 <= last) {
+                uint4 o = *reinterpret_cast<const uint4*>(g + k);
+                o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+                *reinterpret_cast<uint4*>(g + k) = o;
+            } else {
+                const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (e[i] && k + i >= first && k + i < last) g[k + i] += e[i];
+            }
+        }
+    }
+}
+
+// depth = A + C + G + T + DEL; the base allele is ref (0..3) where given,
+// else the allele with the highest count (ties: the lowest channel); alt the
+// highest count among the other four.  64-bit integers only.
+__device__ __forceinline__ bool is_site(const uint32_t (&a)[5], int ref, const SiteArgs& s) {
+    const unsigned long long depth = (unsigned long long)a[0] + a[1] + a[2] + a[3] + a[4];
+    int base = 0;
+    if (ref >= 0 && ref < 4) {
+        base = ref;
+    } else {
+#pragma unroll
+        for (int i = 1; i < 5; ++i)
+            if (a[i] > a[base]) base = i;
+    }
+    unsigned long long alt = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+        if (i != base && a[i] > alt) alt = a[i];
+    return depth >= s.min_depth && alt >= s.min_count && alt * 1000000ull >= s.min_ppm * depth;
+}
+
+// Bit r of the result: position r * kThreads + threadIdx.x of tile t is a site.
+__device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ planes, int64_t stride,
+                                               const uint8_t* __restrict__ ref, const Tile& t,
+                                               const SiteArgs& s) {
+    uint32_t fm = 0;
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const int k = r * kThreads + (int)threadIdx.x;
+        if (k < t.n) {
+            const int64_t i = t.out + k;
+            const uint32_t a[5] = {planes[i], planes[stride + i], planes[2 * stride + i], planes[3 * stride + i],
+                                   planes[5 * stride + i]};
+            fm |= (uint32_t)is_site(a, ref ? (int)ref[i] : 4, s) << r;
+        }
+    }
+    return fm;
+}
+
+__global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* __restrict__ planes, int64_t stride,
+                                                              const uint8_t* __restrict__ ref,
+                                                              const Tile* __restrict__ tiles, SiteArgs s,
+                                                              int32_t* __restrict__ counts) {
+    __shared__ int32_t wsum[kWaves];
+    const Tile t = tiles[blockIdx.x];
+    int32_t c = __popc(site_flags(planes, stride, ref, t, s));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t sum = 0;
+        for (int i = 0; i < kWaves; ++i) sum += wsum[i];
+        counts[blockIdx.x] = sum;
+    }
+}
+
+// One workgroup.  base[i] = sum of counts[0, i) for i <= n_tiles, then
+// seg_first[s] = base[seg_tile[s]] for s <= S (runs.hip's scan).
+__global__ __launch_bounds__(kScanThreads) void sites_scan_kernel(const int32_t* __restrict__ counts,
+                                                                 int64_t n_tiles, int64_t* __restrict__ base,
+                                                                 const int64_t* __restrict__ seg_tile, int64_t S,
+                                                                 int64_t* __restrict__ seg_first) {
+    __shared__ int32_t wsum[kScanThreads / 64];
+    __shared__ int64_t carry_s;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (int64_t i0 = 0; i0 < n_tiles; i0 += kScanWidth) {
+        const int64_t i = i0 + 4 * (int64_t)t;
+        int32_t c[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = i + k < n_tiles ? counts[i + k] : 0;
+        const int32_t mine = c[0] + c[1] + c[2] + c[3];     // <= 4 kTile; an iteration's sum < 2^24
+        int32_t inc = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t o = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += o;
+        }
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        int32_t wbase = 0, total = 0;
+        for (int w = 0; w < kScanThreads / 64; ++w) {
+            if (w < wave) wbase += wsum[w];
+            total += wsum[w];
+        }
+        int64_t bs = carry_s + wbase + (inc - mine);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i + k < n_tiles) base[i + k] = bs;
+            bs += c[k];
+        }
+        __syncthreads();                                    // every thread has read carry_s and wsum
+        if (t == 0) carry_s += total;
+        __syncthreads();
+    }
+    if (t == 0) base[n_tiles] = carry_s;
+    __syncthreads();                                        // base[] is visible to this workgroup
+    for (int64_t s = t; s <= S; s += kScanThreads) seg_first[s] = base[seg_tile[s]];
+}
+
+__global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __restrict__ planes, int64_t stride,
+                                                             const uint8_t* __restrict__ ref,
+                                                             const Tile* __restrict__ tiles, SiteArgs s,
+                                                             const int64_t* __restrict__ base,
+                                                             int64_t* __restrict__ site_pos,
+                                                             uint32_t* __restrict__ site_counts) {
+    __shared__ int32_t wcnt[kRounds][kWaves];
+    const Tile t = tiles[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t fm = site_flags(planes, stride, ref, t, s);
+    int32_t rank[kRounds];                                  // sites of this round in lower lanes of the wave
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const unsigned long long m = __ballot((fm >> r) & 1);
+        rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        if (lane == 0) wcnt[r][wave] = __popcll(m);
+    }
+    __syncthreads();
+    int64_t run = base[blockIdx.x];                         // positions ascend with (round, wave, lane)
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        int64_t mine = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            if (w == wave) mine = run;
+            run += wcnt[r][w];
+        }
+        if ((fm >> r) & 1) {
+            const int k = r * kThreads + (int)threadIdx.x;
+            const int64_t o = mine + rank[r], i = t.out + k;
+            site_pos[o] = t.rel + k;
+#pragma unroll
+            for (int c = 0; c < kPlanes; ++c) site_counts[o * kPlanes + c] = planes[c * stride + i];
+        }
+    }
+}
+
+}  // namespace
+
+#define HIP_TRY(expr)                                                          \
+    do {                                                                       \
+        hipError_t e_ = (expr);                                                \
+        if (e_ != hipSuccess) {                                                \
+            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                          __FILE__, __LINE__);                                 \
+            return MC_E_HIP;                                                   \
+        }                                                                      \
+    } while (0)
+
+namespace {
+
+constexpr size_t kArenaPad = 64;   // bytes behind every uploaded array
+
+// grow-only device array, kArenaPad bytes of room behind the n elements asked for
+template <typename T>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = std::max(n, (size_t)256);
+        hipError_t e = hipMalloc(&p, want * sizeof(T) + kArenaPad);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    ~Buf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+}  // namespace
+
+struct mc_bases {
+    int device = 0;
+    int32_t n_ref = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned long long* pin = nullptr;   // [0] lowest bad read, [1] max span (int32), [2] site total
+    // segments and planes (mc_bases_begin)
+    bool begun = false;
+    int32_t min_baseq = 0;
+    int64_t S = 0, N = 0, stride = 4, n_tiles = 0;
+    std::vector<int64_t> seg_off;
+    Buf<Tile> tiles;
+    Buf<int32_t> order;                  // the tiles sorted by (tid, rel)
+    std::vector<std::pair<int32_t, int64_t>> tile_key;   // (tid, rel) of order[i], on the host
+    Buf<int64_t> seg_tile;
+    Buf<uint32_t> planes;
+    // the batch in flight
+    Buf<int32_t> tid, pos, l_seq, span;
+    Buf<int64_t> cig_off, seq_off, qual_off;
+    Buf<uint32_t> cigar;
+    Buf<uint8_t> seq, qual;
+    Buf<unsigned long long> flags;       // [0] lowest bad read, [1] max span
+    bool have_last = false;
+    int32_t last_tid = 0, last_pos = 0;
+    int64_t n_reads = 0;
+    // sites
+    bool have_sites = false;
+    int64_t n_sites = 0;
+    Buf<uint8_t> ref;
+    Buf<int32_t> counts;
+    Buf<int64_t> base, site_first, site_pos;
+    Buf<uint32_t> site_counts;
+    float ms_prepass = 0, ms_pileup = 0, ms_sites = 0;
+    ~mc_bases() {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (pin) (void)hipHostFree(pin);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+extern "C" int mc_bases_create(int device, int32_t n_ref, mc_bases** out) {
+    MC_REQUIRE(out, MC_E_INVALID, "null argument");
+    *out = nullptr;
+    MC_REQUIRE(n_ref >= 0, MC_E_INVALID, "n_ref %d is negative", n_ref);
+    int n_dev = 0;
+    HIP_TRY(hipGetDeviceCount(&n_dev));
+    MC_REQUIRE(device >= 0 && device < n_dev, MC_E_HIP, "no HIP device %d (%d present)", device, n_dev);
+    HIP_TRY(hipSetDevice(device));
+    mc_bases* h = new mc_bases();
+    h->device = device;
+    h->n_ref = n_ref;
+    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
+              hipHostMalloc((void**)&h->pin, 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
+              h->flags.reserve(2) == hipSuccess;
+    for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    if (!ok) {
+        delete h;
+        mc::set_error("HIP stream / event creation failed");
+        return MC_E_HIP;
+    }
+    *out = h;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_destroy(mc_bases* h) {
+    if (h) {
+        (void)hipSetDevice(h->device);
+        delete h;
+    }
+    return MC_OK;
+}
+
+extern "C" int mc_bases_dims(int32_t* tile) {
+    MC_REQUIRE(tile, MC_E_INVALID, "null argument");
+    *tile = kTile;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const int64_t* start, const int64_t* end,
+                              int32_t min_baseq) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(S >= 0 && (S == 0 || (tid && start && end)), MC_E_INVALID, "bad segment arrays");
+    MC_REQUIRE(min_baseq >= 0, MC_E_INVALID, "min_baseq %d is negative", min_baseq);
+    h->begun = false;
+    h->have_sites = false;
+
+    // ---- tile table (host): a tile never spans two segments
+    std::vector<Tile> tiles;
+    std::vector<int64_t> seg_tile((size_t)S + 1), seg_off((size_t)S + 1);
+    int64_t N = 0;
+    for (int64_t s = 0; s < S; ++s) {
+        MC_REQUIRE(tid[s] >= 0 && tid[s] < h->n_ref, MC_E_INVALID, "segment %lld: tid %d out of range",
+                   (long long)s, tid[s]);
+        MC_REQUIRE(start[s] >= 0 && end[s] >= start[s] && end[s] <= kMaxPos, MC_E_INVALID,
+                   "segment %lld: bad range [%lld, %lld)", (long long)s, (long long)start[s], (long long)end[s]);
+        seg_tile[s] = (int64_t)tiles.size();
+        seg_off[s] = N;
+        for (int64_t a = start[s]; a < end[s];) {
+            Tile t;
+            t.out = N;
+            t.rel = a;
+            t.lead = (int32_t)(N & 3);
+            t.n = (int32_t)std::min<int64_t>(kTile - t.lead, end[s] - a);
+            t.tid = tid[s];
+            t.seg = (int32_t)std::min<int64_t>(s, INT32_MAX);
+            tiles.push_back(t);
+            a += t.n;
+            N += t.n;
+            MC_REQUIRE(tiles.size() < (size_t)INT32_MAX, MC_E_RANGE, "more than 2^31 tiles of %d positions",
+                       kTile);
+        }
+    }
+    const int64_t T = (int64_t)tiles.size();
+    seg_tile[S] = T;
+    seg_off[S] = N;
+    for (int64_t s = S - 1; s >= 0; --s)          // an empty segment: the next non-empty one's first tile
+        if (end[s] == start[s]) seg_tile[s] = seg_tile[s + 1];
+    const int64_t stride = std::max<int64_t>(4, (N + 3) & ~int64_t(3));   // every plane 16-byte aligned
+    // the tiles in (tid, rel) order: a batch launches only the range of them its reads can reach
+    std::vector<int32_t> order((size_t)T);
+    for (int64_t i = 0; i < T; ++i) order[(size_t)i] = (int32_t)i;
+    std::sort(order.begin(), order.end(), [&tiles](int32_t a, int32_t b) {
+        return tiles[a].tid != tiles[b].tid ? tiles[a].tid < tiles[b].tid : tiles[a].rel < tiles[b].rel;
+    });
+    std::vector<std::pair<int32_t, int64_t>> tile_key((size_t)T);
+    for (int64_t i = 0; i < T; ++i) tile_key[(size_t)i] = {tiles[order[(size_t)i]].tid, tiles[order[(size_t)i]].rel};
+
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->tiles.reserve((size_t)T));
+    HIP_TRY(h->order.reserve((size_t)T));
+    HIP_TRY(h->seg_tile.reserve((size_t)S + 1));
+    HIP_TRY(h->planes.reserve((size_t)(kPlanes * stride)));
+    hipStream_t st = h->stream;
+    if (T) HIP_TRY(hipMemcpyAsync(h->tiles.p, tiles.data(), (size_t)T * sizeof(Tile), hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(h->order.p, order.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->seg_tile.p, seg_tile.data(), ((size_t)S + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->planes.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
+    HIP_TRY(hipStreamSynchronize(st));            // the host vectors are released
+    h->S = S;
+    h->N = N;
+    h->stride = stride;
+    h->n_tiles = T;
+    h->seg_off = std::move(seg_off);
+    h->tile_key = std::move(tile_key);
+    h->min_baseq = min_baseq;
+    h->have_last = false;
+    h->n_reads = 0;
+    h->ms_prepass = h->ms_pileup = h->ms_sites = 0;
+    h->begun = true;
+    return MC_OK;
+}
+
+namespace {
+
+// Why read i of the batch is invalid, for mc_last_error (the pre-pass found i).
+void name_bad_read(const mc_bases* h, int64_t i, const int32_t* tid, const int32_t* pos, const int64_t* cig_off,
+                   const uint32_t* cigar, const int32_t* l_seq, const int64_t* seq_off, const int64_t* qual_off,
+                   int64_t n_words, int64_t seq_bytes, int64_t qual_bytes) {
+    const long long r = (long long)i;
+    if (tid[i] < 0 || tid[i] >= h->n_ref) return mc::set_error("read %lld: tid %d out of range", r, tid[i]);
+    if (pos[i] < 0) return mc::set_error("read %lld: negative pos %d", r, pos[i]);
+    if (l_seq[i] < 0) return mc::set_error("read %lld: negative l_seq %d", r, l_seq[i]);
+    if (cig_off[i] < 0 || cig_off[i + 1] < cig_off[i] || cig_off[i + 1] > n_words)
+        return mc::set_error("read %lld: CIGAR offsets outside the batch", r);
+    if (seq_off[i] < 0 || seq_off[i] + ((int64_t)l_seq[i] + 1) / 2 > seq_bytes || qual_off[i] < 0 ||
+        qual_off[i] + l_seq[i] > qual_bytes)
+        return mc::set_error("read %lld: bases or qualities outside the batch", r);
+    if (i > 0 && (tid[i - 1] > tid[i] || (tid[i - 1] == tid[i] && pos[i - 1] > pos[i])))
+        return mc::set_error("read %lld: reads are not sorted by (tid, pos)", r);
+    int64_t q = 0, ref = 0;
+    for (int64_t k = cig_off[i]; k < cig_off[i + 1]; ++k) {
+        const uint32_t op = cigar[k] & 15u;
+        if ((kQueryOps >> op) & 1u) q += cigar[k] >> 4;
+        if ((kRefOps >> op) & 1u) ref += cigar[k] >> 4;
+    }
+    if (q != l_seq[i])
+        return mc::set_error("read %lld: CIGAR query length %lld differs from l_seq %d", r, (long long)q, l_seq[i]);
+    mc::set_error("read %lld: reference span %lld exceeds 2^31 - 1", r, (long long)ref);
+}
+
+}  // namespace
+
+extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                                  const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
+                                  const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
+                                  const uint8_t* qual) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
+    if (n == 0) return MC_OK;
+    MC_REQUIRE(tid && pos && cig_off && l_seq && seq_off && qual_off, MC_E_INVALID, "null read arrays");
+    const int64_t n_words = cig_off[n], seq_bytes = seq_off[n], qual_bytes = qual_off[n];
+    MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
+    MC_REQUIRE((n_words == 0 || cigar) && (seq_bytes == 0 || seq) && (qual_bytes == 0 || qual), MC_E_INVALID,
+               "null arena");
+    if (h->have_last && tid[0] >= 0 && pos[0] >= 0)
+        MC_REQUIRE(h->last_tid < tid[0] || (h->last_tid == tid[0] && h->last_pos <= pos[0]), MC_E_INVALID,
+                   "read 0: reads are not sorted by (tid, pos) against the previous batch");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->tid.reserve((size_t)n));
+    HIP_TRY(h->pos.reserve((size_t)n));
+    HIP_TRY(h->l_seq.reserve((size_t)n));
+    HIP_TRY(h->span.reserve((size_t)n));
+    HIP_TRY(h->cig_off.reserve((size_t)n + 1));
+    HIP_TRY(h->seq_off.reserve((size_t)n + 1));
+    HIP_TRY(h->qual_off.reserve((size_t)n + 1));
+    HIP_TRY(h->cigar.reserve((size_t)n_words));
+    HIP_TRY(h->seq.reserve((size_t)seq_bytes));
+    HIP_TRY(h->qual.reserve((size_t)qual_bytes));
+    hipStream_t st = h->stream;
+    const auto up = [st](void* d, const void* s, size_t bytes) {
+        return bytes ? hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(up(h->tid.p, tid, (size_t)n * 4));
+    HIP_TRY(up(h->pos.p, pos, (size_t)n * 4));
+    HIP_TRY(up(h->l_seq.p, l_seq, (size_t)n * 4));
+    HIP_TRY(up(h->cig_off.p, cig_off, ((size_t)n + 1) * 8));
+    HIP_TRY(up(h->seq_off.p, seq_off, ((size_t)n + 1) * 8));
+    HIP_TRY(up(h->qual_off.p, qual_off, ((size_t)n + 1) * 8));
+    HIP_TRY(up(h->cigar.p, cigar, (size_t)n_words * 4));
+    HIP_TRY(up(h->seq.p, seq, (size_t)seq_bytes));
+    HIP_TRY(up(h->qual.p, qual, (size_t)qual_bytes));
+    h->pin[0] = kNoBad;
+    h->pin[1] = 0;
+    HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
+    Batch b{h->tid.p, h->pos.p, h->l_seq.p, h->cig_off.p, h->cigar.p, h->seq_off.p, h->seq.p,
+            h->qual_off.p, h->qual.p, n, n_words, seq_bytes, qual_bytes};
+    const int64_t groups = (n + kThreads - 1) / kThreads;
+    MC_REQUIRE(groups < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^39 reads in one batch");
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(bases_prepass_kernel, dim3((unsigned)groups), dim3(kThreads), 0, st, b, h->n_ref, h->span.p,
+                       h->flags.p, reinterpret_cast<int32_t*>(h->flags.p + 1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    HIP_TRY(hipMemcpyAsync(h->pin, h->flags.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const unsigned long long bad = h->pin[0];
+    if (bad != kNoBad) {
+        if (bad < (unsigned long long)n)
+            name_bad_read(h, (int64_t)bad, tid, pos, cig_off, cigar, l_seq, seq_off, qual_off, n_words, seq_bytes,
+                          qual_bytes);
+        else
+            mc::set_error("read index %llu out of range", bad);
+        return MC_E_INVALID;
+    }
+    int32_t max_span = 0;
+    std::memcpy(&max_span, &h->pin[1], 4);
+    MC_REQUIRE(max_span >= 0, MC_E_STATE, "maximum span %d out of range", max_span);
+    HIP_TRY(hipEventRecord(h->ev[2], st));
+    // A tile the batch can reach starts after (first read's pos - kTile) and before (last read's pos +
+    // max span), in (tid, rel) order: only that range of the sorted tiles is launched.
+    const auto t_lo = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
+                                       std::make_pair(tid[0], (int64_t)pos[0] - kTile));
+    const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
+                                       std::make_pair(tid[n - 1], (int64_t)pos[n - 1] + max_span));
+    if (max_span > 0 && t_lo < t_hi) {
+        hipLaunchKernelGGL(bases_pileup_kernel, dim3((unsigned)(t_hi - t_lo)), dim3(kThreads), 0, st, b, h->span.p,
+                           h->tiles.p, h->order.p + (t_lo - h->tile_key.begin()), max_span, h->min_baseq,
+                           h->planes.p, h->stride);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays and the handle's batch buffers are free again
+    float a = 0, c = 0;
+    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+    h->ms_prepass += a;
+    h->ms_pileup += c;
+    h->have_last = true;
+    h->last_tid = tid[n - 1];
+    h->last_pos = pos[n - 1];
+    h->n_reads += n;
+    h->have_sites = false;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_seg_off(const mc_bases* h, int64_t* seg_off) {
+    MC_REQUIRE(h && seg_off, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    std::memcpy(seg_off, h->seg_off.data(), ((size_t)h->S + 1) * 8);
+    return MC_OK;
+}
+
+extern "C" int mc_bases_get(const mc_bases* h, int64_t first, int64_t count, uint32_t* out) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
+               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
+               (long long)count, (long long)h->N);
+    MC_REQUIRE(count == 0 || out, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    for (int c = 0; c < kPlanes; ++c)
+        HIP_TRY(hipMemcpyAsync(out + (size_t)c * (size_t)count, h->planes.p + c * h->stride + first, (size_t)count * 4,
+                               hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_device(const mc_bases* h, const uint32_t** d_planes, int64_t* stride, int64_t* n) {
+    MC_REQUIRE(h && d_planes && stride && n, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    *d_planes = h->planes.p;
+    *stride = h->stride;
+    *n = h->N;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                              const uint8_t* ref, int64_t* n_sites) {
+    MC_REQUIRE(h && n_sites, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(min_depth >= 0 && min_count >= 0 && min_ppm >= 0 && min_ppm <= 1000000, MC_E_INVALID,
+               "site thresholds out of range (min_depth %lld, min_count %lld, min_ppm %lld of 10^6)",
+               (long long)min_depth, (long long)min_count, (long long)min_ppm);
+    h->have_sites = false;
+    const int64_t T = h->n_tiles, S = h->S;
+    const SiteArgs sa{(unsigned long long)min_depth, (unsigned long long)min_count, (unsigned long long)min_ppm};
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->counts.reserve((size_t)T));
+    HIP_TRY(h->base.reserve((size_t)T + 1));
+    HIP_TRY(h->site_first.reserve((size_t)S + 1));
+    hipStream_t st = h->stream;
+    const uint8_t* d_ref = nullptr;
+    if (ref && h->N) {
+        HIP_TRY(h->ref.reserve((size_t)h->N));
+        HIP_TRY(hipMemcpyAsync(h->ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, st));
+        d_ref = h->ref.p;
+    }
+    HIP_TRY(hipEventRecord(h->ev[4], st));
+    if (T) {
+        hipLaunchKernelGGL(sites_count_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
+                           h->tiles.p, sa, h->counts.p);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->counts.p, T, h->base.p,
+                       h->seg_tile.p, S, h->site_first.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->pin + 2, h->base.p + T, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int64_t total = 0;
+    std::memcpy(&total, h->pin + 2, 8);
+    MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "site count %lld out of range", (long long)total);
+    HIP_TRY(h->site_pos.reserve((size_t)total));
+    HIP_TRY(h->site_counts.reserve((size_t)total * kPlanes));
+    if (T) {
+        hipLaunchKernelGGL(sites_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
+                           h->tiles.p, sa, h->base.p, h->site_pos.p, h->site_counts.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[5], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&h->ms_sites, h->ev[4], h->ev[5]));   // (the 8-byte read-back included)
+    h->n_sites = total;
+    h->have_sites = true;
+    *n_sites = total;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_sites_first(const mc_bases* h, int64_t* site_first) {
+    MC_REQUIRE(h && site_first, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_sites, MC_E_STATE, "no sites computed (call mc_bases_sites)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(site_first, h->site_first.p, ((size_t)h->S + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_sites_get(const mc_bases* h, int64_t first, int64_t count, int64_t* site_pos,
+                                  uint32_t* site_counts) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_sites, MC_E_STATE, "no sites computed (call mc_bases_sites)");
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->n_sites && count <= h->n_sites - first, MC_E_INVALID,
+               "sites [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count,
+               (long long)h->n_sites);
+    MC_REQUIRE(count == 0 || (site_pos && site_counts), MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(site_pos, h->site_pos.p + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(site_counts, h->site_counts.p + first * kPlanes, (size_t)count * kPlanes * 4,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pileup_ms, float* sites_ms,
+                               int64_t* tiles, int64_t* reads) {
+    MC_REQUIRE(h && prepass_ms && pileup_ms && sites_ms && tiles && reads, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    *prepass_ms = h->ms_prepass;
+    *pileup_ms = h->ms_pileup;
+    *sites_ms = h->ms_sites;
+    *tiles = h->n_tiles;
+    *reads = h->n_reads;
+    return MC_OK;
+}
