@@ -465,6 +465,22 @@ int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t
                        const int64_t* cig_off /* n + 1 */, const uint32_t* cigar, const int32_t* l_seq,
                        const int64_t* seq_off /* n + 1 */, const uint8_t* seq,
                        const int64_t* qual_off /* n + 1 */, const uint8_t* qual);
+/* mc_bases_add_batch with the nine arrays in device memory on the handle's
+ * device (e.g. mc_bam_gpu_bases_device's): same reads, same checks, same
+ * error classes and messages, same kernels, no copies of the arrays.  The
+ * offsets are absolute into the arenas and the arena sizes are explicit
+ * (n_words, seq_bytes, qual_bytes), so a sub-range [a, a + n) of a resident
+ * read table is d_tid + a, d_pos + a, d_cig_off + a, d_l_seq + a, d_seq_off + a
+ * and d_qual_off + a with the arena pointers and sizes unchanged.  The first
+ * and last read's (tid, pos) (the tile range, the order check across batches)
+ * come back with the pre-pass flags in one 32-byte copy; only for an invalid
+ * batch are the bad read's fields and CIGAR words copied back to name it.
+ * Returns after its kernels, so the memory may be freed afterwards. */
+int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                              const int64_t* d_cig_off /* n + 1 */, const uint32_t* d_cigar, int64_t n_words,
+                              const int32_t* d_l_seq, const int64_t* d_seq_off /* n + 1 */, const uint8_t* d_seq,
+                              int64_t seq_bytes, const int64_t* d_qual_off /* n + 1 */, const uint8_t* d_qual,
+                              int64_t qual_bytes);
 int mc_bases_seg_off(const mc_bases* h, int64_t* seg_off /* S + 1 */);
 int mc_bases_get(const mc_bases* h, int64_t first, int64_t count, uint32_t* out /* 6 x count */);
 int mc_bases_device(const mc_bases* h, const uint32_t** d_planes, int64_t* stride, int64_t* n);
@@ -678,6 +694,41 @@ int mc_bam_gpu_reads_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_t
                             const uint8_t** d_names, int64_t* name_bytes);
 int mc_bam_gpu_reads_copy(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int64_t* end, int32_t* flag,
                           uint8_t* bits, uint32_t* kmer, uint8_t* name_len, int64_t* name_off, uint8_t* names);
+/* The base counter's input decoded on the GPU (the device form of
+ * mc_bases_src_*: same kept set, same skips, same counts, same layout).  The
+ * whole file is decoded, windowed as the other modes; the records
+ * mc_bases_src_next would hand out stay in device memory owned by the handle,
+ * in file order, as one read table in mc_bases_add_batch's layout: tid, pos
+ * and l_seq [n], cig_off, seq_off and qual_off [n + 1] (absolute offsets, the
+ * last one the arena's size), and three arenas: CIGAR words (the CG:B,I words
+ * where the record carries the tag), nt16 bytes (every read starts on a 4-byte
+ * boundary, zero fill) and quality bytes (packed).  mc_bam_gpu_bases_device
+ * gives the device pointers, n and the arena sizes (valid until
+ * mc_bam_gpu_close; hand them, or a sub-range of the reads, to
+ * mc_bases_add_batch_device); mc_bam_gpu_bases_copy copies the table to host
+ * buffers of those sizes (tests, debugging); mc_bam_gpu_bases_counts gives
+ * mc_bases_src_counts' four numbers.  The sort order is not checked here (the
+ * base counter's pre-pass checks it); a record that is malformed for
+ * mc_bases_src_next is MC_E_IO.  Device work: a count and a fill walk with one
+ * lane per 64 KiB segment (the fill writes the columns, the offsets and each
+ * read's source offsets), then a gather kernel that copies CIGAR, SEQ and QUAL
+ * with 16 lanes per read.  If the table outgrows device memory the open fails
+ * with MC_E_HIP and says so.  mc_bam_gpu_header, _stats, _trim and _close work
+ * as for the other modes; the other modes' accessors (intervals, scan, reads,
+ * extents, restrict) are MC_E_STATE on such a handle, and these three are
+ * MC_E_STATE on any other.  Whole files only (no contig subset, no extents). */
+int mc_bam_gpu_open_bases(const char* path, int device, int n_threads, uint32_t flag_filter, int min_mapq,
+                          int64_t window_bytes, mc_bam_gpu** out);
+int mc_bam_gpu_bases_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_tid, const int32_t** d_pos,
+                            const int64_t** d_cig_off, const uint32_t** d_cigar, int64_t* n_words,
+                            const int32_t** d_l_seq, const int64_t** d_seq_off, const uint8_t** d_seq,
+                            int64_t* seq_bytes, const int64_t** d_qual_off, const uint8_t** d_qual,
+                            int64_t* qual_bytes);
+int mc_bam_gpu_bases_copy(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int64_t* cig_off /* n + 1 */,
+                          uint32_t* cigar, int32_t* l_seq, int64_t* seq_off /* n + 1 */, uint8_t* seq,
+                          int64_t* qual_off /* n + 1 */, uint8_t* qual);
+int mc_bam_gpu_bases_counts(const mc_bam_gpu* g, int64_t* records, int64_t* kept, int64_t* no_seq,
+                            int64_t* bad_cigar);
 /* The same for one rank's contigs (mc_bam_gpu_open_extents' blocks and
  * extents table: only the selected contigs' BGZF blocks are read and
  * inflated); tids stay the header's.  The header counts are the table's. */
@@ -733,6 +784,14 @@ int mc_bam_gpu_intervals_range(const mc_bam_gpu* g, int64_t first, int64_t count
 int mc_gz_inflate_host(const uint8_t* src, int64_t clen, uint8_t* dst, int64_t isize);
 int mc_bam_rec_parse_host(const uint8_t* r, int64_t len, int32_t n_ref, uint32_t flag_filter,
                           int32_t* out3);
+/* mc_bam_rec_bases_host: the bases-mode record rule for the record body
+ * r[0, len) -> 0 dropped by the filters, 1 taken (out7 = tid, pos, l_seq, the
+ * CIGAR word count, and the offsets in r of the CIGAR words, of SEQ and of
+ * QUAL), 2 kept without SEQ, 3 kept with a CIGAR query length other than
+ * l_seq, 4 malformed (l_seq < 0; CIGAR, SEQ or QUAL past len; tid outside
+ * [-1, n_ref); len < 32).  Reads nothing outside r[0, len). */
+int mc_bam_rec_bases_host(const uint8_t* r, int64_t len, int32_t n_ref, uint32_t flag_filter, int32_t min_mapq,
+                          int64_t* out7);
 /* mc_bam_rec_chain_host: 1 if offset q of the inflated stream d[0, n) starts
  * `chain` structurally valid records in sort order (mapped records' bin
  * fields equal to reg2bin of their span), or a shorter such chain ending

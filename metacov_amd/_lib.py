@@ -142,6 +142,7 @@ SIGNATURES = {
     "mc_bases_destroy": [_P],
     "mc_bases_begin": [_P, _I64, _P, _P, _P, _I32],
     "mc_bases_add_batch": [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mc_bases_add_batch_device": [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _I64],
     "mc_bases_seg_off": [_P, _P],
     "mc_bases_get": [_P, _I64, _I64, _P],
     "mc_bases_device": [_P, _PP, _PI64, _PI64],
@@ -193,6 +194,10 @@ SIGNATURES = {
     "mc_bam_gpu_reads_copy": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mc_bam_gpu_open_reads_extents": [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _I32, _P, _I64,
                                       _I32, _P, _PP],
+    "mc_bam_gpu_open_bases": [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _U32, ctypes.c_int, _I64, _PP],
+    "mc_bam_gpu_bases_device": [_P, _PI64, _PP, _PP, _PP, _PP, _PI64, _PP, _PP, _PP, _PI64, _PP, _PP, _PI64],
+    "mc_bam_gpu_bases_copy": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mc_bam_gpu_bases_counts": [_P, _PI64, _PI64, _PI64, _PI64],
     "mc_bam_index_extents": [ctypes.c_char_p, _I32, _P, _PI64],
     "mc_bam_gpu_open_contigs": [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _U32, _I32, _P,
                                 _PP],
@@ -203,6 +208,7 @@ SIGNATURES = {
     "mc_bam_gpu_intervals_range": [_P, _I64, _I64, _P, _P, _P],
     "mc_gz_inflate_host": [_P, _I64, _P, _I64],
     "mc_bam_rec_parse_host": [_P, _I64, _I32, _U32, _P],
+    "mc_bam_rec_bases_host": [_P, _I64, _I32, _U32, _I32, _PI64],
     "mc_bam_rec_chain_host": [_P, _I64, _I64, _I32, ctypes.c_int],
     "mc_bgzf_scan_host": [ctypes.c_char_p, ctypes.c_int, _PI64, _PI64, _PI64, _I64],
     "mc_gz_inflate_device": [ctypes.c_int, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _I32, _P],

@@ -10,8 +10,10 @@
 
 The pileup runs on the GPU (csrc/bases.hip, mc_bases_* in
 include/metacov_amd.h); the records come from the host source in
-csrc/bases_src.cpp, so file decode, not the kernel, bounds the path end to
-end.  These are the numbers of pysam's `AlignmentFile.count_coverage()`,
+csrc/bases_src.cpp (decode="host", the default: file decode on host threads
+bounds the path end to end) or from the GPU decoder's bases mode
+(decode="gpu", GpuBaseSource: the records stay in device memory between
+decode and pileup).  These are the numbers of pysam's `AlignmentFile.count_coverage()`,
 `samtools mpileup`, pysamstats and bam-readcount; the reference has no
 counterpart.  The contract (CIGAR walk, channels, quality rule, segments,
 sites) is the header's.
@@ -119,6 +121,80 @@ class BaseSource:
         self.close()
 
 
+class GpuBaseSource:
+    """The same records decoded on the GPU (mc_bam_gpu_open_bases): the whole
+    file's read table, in mc_bases_add_batch's layout, resident in device
+    memory until close.  BaseCounter.add_device feeds it; one open source
+    serves any number of begins.  window_bytes: inflated bytes per decode
+    window (0: the decoder's default)."""
+
+    def __init__(self, path, device=0, n_threads=0, flag_filter=FLAG_FILTER, min_mapq=0, window_bytes=0, lib=None):
+        from .bam import _header_of
+        self._lib = lib or _lib.load()
+        self._h = ctypes.c_void_p()
+        self.device = int(device)
+        check(self._lib.mc_bam_gpu_open_bases(str(path).encode(), self.device, int(n_threads), int(flag_filter),
+                                              int(min_mapq), int(window_bytes), ctypes.byref(self._h)), self._lib)
+        hdr = ctypes.c_void_p()
+        check(self._lib.mc_bam_gpu_header(self._h, ctypes.byref(hdr)), self._lib)
+        names, lengths, _ = _header_of(self._lib, hdr)
+        self.references, self.lengths = list(names), list(lengths)
+        # what add_device needs of the table: n, the sizes, the device pointers
+        n, nw, sb, qb = (ctypes.c_int64() for _ in range(4))
+        p = [ctypes.c_void_p() for _ in range(9)]
+        r = ctypes.byref
+        check(self._lib.mc_bam_gpu_bases_device(self._h, r(n), r(p[0]), r(p[1]), r(p[2]), r(p[3]), r(nw), r(p[4]),
+                                                r(p[5]), r(p[6]), r(sb), r(p[7]), r(p[8]), r(qb)), self._lib)
+        self.n = n.value
+        self.n_words, self.seq_bytes, self.qual_bytes = nw.value, sb.value, qb.value
+        self._dptr = [x.value or 0 for x in p]   # tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual
+        self._lib.mc_bam_gpu_trim(self._h, None)  # the decode's staging is not needed again
+
+    def __len__(self):
+        return self.n
+
+    def counts(self):
+        """The whole file's record counts (BaseSource.counts at its end)."""
+        v = [ctypes.c_int64() for _ in range(4)]
+        check(self._lib.mc_bam_gpu_bases_counts(self._h, *[ctypes.byref(x) for x in v]), self._lib)
+        return dict(zip(("records", "kept", "no_seq", "bad_cigar"), (x.value for x in v)))
+
+    def timings(self):
+        t = _lib.GpuDecodeTimings()
+        check(self._lib.mc_bam_gpu_stats(self._h, ctypes.byref(t)), self._lib)
+        return {k: getattr(t, k) for k, _ in t._fields_}
+
+    def copy(self):
+        """The read table on the host: a dict with BaseSource.next's keys."""
+        n = self.n
+        out = {"tid": np.zeros(n, np.int32), "pos": np.zeros(n, np.int32), "cig_off": np.zeros(n + 1, np.int64),
+               "cigar": np.zeros(self.n_words, np.uint32), "l_seq": np.zeros(n, np.int32),
+               "seq_off": np.zeros(n + 1, np.int64), "seq": np.zeros(self.seq_bytes, np.uint8),
+               "qual_off": np.zeros(n + 1, np.int64), "qual": np.zeros(self.qual_bytes, np.uint8)}
+        check(self._lib.mc_bam_gpu_bases_copy(self._h, *[ctypes.c_void_p(out[k].ctypes.data) if out[k].size else None
+                                                         for k in ("tid", "pos", "cig_off", "cigar", "l_seq",
+                                                                   "seq_off", "seq", "qual_off", "qual")]),
+              self._lib)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mc_bam_gpu_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class BaseCounter:
     """One mc_bases (device buffers that only grow, reused between begins)."""
 
@@ -177,10 +253,42 @@ class BaseCounter:
         check(self._lib.mc_bases_add_batch(self._h, n, ptr(tid), ptr(pos), ptr(cig_off), ptr(cigar), ptr(l_seq),
                                            ptr(seq_off), ptr(seq), ptr(qual_off), ptr(qual)), self._lib)
 
+    def add_device(self, src, max_reads=1 << 20):
+        """Every read of an open GpuBaseSource, straight from device memory
+        (mc_bases_add_batch_device), in sub-ranges of max_reads reads of the
+        resident table: add_bam's batch size, so one long read widens the
+        tile search window of its own batch only."""
+        if src.device != self.device:
+            raise ValueError("the source is on device %d, the counter on device %d" % (src.device, self.device))
+        if max_reads < 1:
+            raise ValueError("max_reads must be positive")
+        tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual = src._dptr
+
+        def at(base, a, size):
+            return ctypes.c_void_p(base + a * size) if base else None
+
+        for a in range(0, src.n, int(max_reads)):
+            n = min(int(max_reads), src.n - a)
+            check(self._lib.mc_bases_add_batch_device(
+                self._h, n, at(tid, a, 4), at(pos, a, 4), at(cig_off, a, 8), at(cigar, 0, 4), src.n_words,
+                at(l_seq, a, 4), at(seq_off, a, 8), at(seq, 0, 1), src.seq_bytes, at(qual_off, a, 8),
+                at(qual, 0, 1), src.qual_bytes), self._lib)
+        if src.n == 0:       # (the state check of an empty batch, as add_reads makes it)
+            check(self._lib.mc_bases_add_batch_device(self._h, 0, None, None, None, None, 0, None, None, None, 0,
+                                                      None, None, 0), self._lib)
+
     def add_bam(self, path, flag_filter=FLAG_FILTER, min_mapq=0, max_reads=1 << 20, max_bases=1 << 27,
-                n_threads=0):
+                n_threads=0, decode="host"):
         """Every kept record of a coordinate-sorted BAM, batch by batch;
-        returns the source's record counts."""
+        returns the source's record counts.  decode: "host" (BaseSource) or
+        "gpu" (GpuBaseSource and add_device: the records never leave the
+        device; max_bases does not apply)."""
+        if decode not in ("host", "gpu"):
+            raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
+        if decode == "gpu":
+            with GpuBaseSource(path, self.device, n_threads, flag_filter, min_mapq, lib=self._lib) as src:
+                self.add_device(src, max_reads)
+                return src.counts()
         with BaseSource(path, n_threads, flag_filter, min_mapq, self._lib) as src:
             while True:
                 b = src.next(max_reads, max_bases)
@@ -233,10 +341,12 @@ class BaseCounter:
                 "reads": r.value}
 
 
-def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, min_mapq=0, device=0):
+def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, min_mapq=0, device=0, decode="host"):
     """pysam's AlignmentFile.count_coverage(contig, start, stop,
     quality_threshold) with read_callback='all': four uint32 arrays A, C, G, T
-    of stop - start counts (default: the whole contig)."""
+    of stop - start counts (default: the whole contig).  decode: as add_bam."""
+    if decode not in ("host", "gpu"):
+        raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
     lib = _lib.load()
     with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
         names = [w.split()[0] if w.split() else w for w in src.references]
@@ -250,7 +360,7 @@ def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, mi
         raise ValueError("bad range [%d, %d)" % (start, stop))
     with BaseCounter(len(names), device, lib) as bc:
         bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
-        bc.add_bam(path, min_mapq=min_mapq)
+        bc.add_bam(path, min_mapq=min_mapq, decode=decode)
         planes = bc.counts()
     return planes[A].copy(), planes[C].copy(), planes[G].copy(), planes[T].copy()
 

@@ -36,10 +36,12 @@ Base counts (no counterpart in the reference either):
 
     python -m metacov_amd.cli bases -b X.bam [-o out.tsv] [-f ref.fa] [-rc R.csv | -rb R.blast7] [--min-baseq 0]
                                     [--min-mapq 0] [--min-depth 1] [--min-count 1] [--min-frac 0.0] [--all]
+                                    [--decode host|gpu]
 
 writes `contig pos ref depth A C G T N DEL` for the variant sites, or with
 `--all` for every position, counted on the GPU (metacov_amd/bases.py); one
-process, no read cap, `pos` 1-based.
+process, no read cap, `pos` 1-based.  `--decode gpu` also decodes the BAM on
+the GPU, once, and keeps the records in device memory.
 
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
@@ -740,21 +742,38 @@ def _segment_letters(fa, name, start, end):
 
 
 def write_bases(path, references, tids, starts, ends, outfile, fasta=None, device=0, min_baseq=0, min_mapq=0,
-                min_depth=1, min_count=1, min_ppm=0, every=False):
+                min_depth=1, min_count=1, min_ppm=0, every=False, decode="host"):
     """The base-count table of the segments (header contig ids), group by
-    group (each group is one pass over the BAM), each written before the next
-    is computed.  Returns (lines written, the source's record counts)."""
+    group, each written before the next is computed.  decode "host": each
+    group is one pass over the BAM on host threads; "gpu": the file is decoded
+    once on the device and every group reads the resident records.  Returns
+    (lines written, the source's record counts)."""
     from . import bases as _bases
+    import contextlib
     names = [w.split()[0] if w.split() else w for w in references]
     outfile.write(_bases.HEADER)
     written, counts = 0, None
     if len(tids) == 0:
         return 0, None
     fa = _experimental.FastaFile(fasta) if fasta else None
-    with _bases.BaseCounter(len(references), device) as bc:
+    with contextlib.ExitStack() as stack:
+        bc = stack.enter_context(_bases.BaseCounter(len(references), device))
+        src = None
+        if decode == "gpu":
+            try:
+                src = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
+            except _bases._lib.MetacovError as e:
+                if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
+                    raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
+                                               "run with --decode host (%s)" % (path, device, e))
+                raise
         for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
             bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
-            counts = bc.add_bam(path, min_mapq=min_mapq)
+            if src is not None:
+                bc.add_device(src)
+                counts = src.counts()
+            else:
+                counts = bc.add_bam(path, min_mapq=min_mapq)
             seg_off = bc.seg_off
             letters = None
             if fa is not None:
@@ -805,8 +824,11 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
 @click.option('--all', 'every', is_flag=True, default=False,
               help="Write every position of the regions, not only the sites")
 @click.option('--device', type=int, default=0, help="HIP device ordinal")
+@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
+              help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
+                   "the GPU, the records staying in device memory (the file's reads must fit there)")
 def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, min_baseq, min_mapq, min_depth,
-          min_count, min_frac, every, device):
+          min_count, min_frac, every, device, decode):
     """
     Write per-position base counts and variant sites
 
@@ -842,7 +864,7 @@ def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, 
         ends = np.asarray(lengths, np.int64)
     n, counts = write_bases(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
                             min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth, min_count=min_count,
-                            min_ppm=min_ppm, every=every)
+                            min_ppm=min_ppm, every=every, decode=decode)
     outfile.flush()
     if counts:
         log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"

@@ -26,6 +26,13 @@
 // A window's incomplete last record is carried to the front of the next
 // window's inflated buffer.  The kept intervals stay in HBM
 // (mc_bam_gpu_intervals_device) for mc_add_reads_device.
+//
+// Three more modes share the upload, the inflate, the sync and the rounds of
+// parse_window and differ in the walk: scan mode (scan_walk_kernel: every
+// record as scan's SoA batch), reads mode (reads_walk_kernel: the placed
+// records as pileup.experimental's read table) and bases mode
+// (bases_walk_kernel + bases_gather_kernel: the base counter's records with
+// CIGAR, SEQ and QUAL in three arenas, mc_bases_add_batch's layout).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -518,6 +525,181 @@ reads_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __res
     }
 }
 
+// Bases mode (the base counter's input, bases_src.cpp's next_batch on the
+// device): the records mc::gz::rec_bases takes, in file order, as
+// mc_bases_add_batch's layout: tid, pos, l_seq, and each read's CIGAR words
+// (CG:B,I resolved), packed nt16 bases (4-byte aligned starts, zero fill) and
+// qualities (packed) in three arenas behind cig_off / seq_off / qual_off
+// [n + 1].  What a segment's walk counts besides SegRes (kept there: the
+// records taken; bytes: unused):
+struct SegBases {
+    int64_t passed;               // records past the filters (taken + no_seq + bad_cigar)
+    int64_t no_seq, bad_cigar;
+    int64_t words, seq_bytes, qual_bytes;   // arena sizes of the records taken (seq_bytes: each rounded up to 4)
+};
+
+// One lane per segment, as rec_walk_kernel.  kFill: read w of the table gets
+// its columns, the ends of its three arena ranges (the offsets of read w + 1)
+// and the offsets of its CIGAR, SEQ and QUAL in the inflated stream
+// (src[3 * (w - w_base) ..]) for bases_gather_kernel; a lane writes only
+// reads [out_off[i], + res[i].kept) and only while its arena ranges stay
+// inside the sizes its count pass gave (arena[i]).
+template <bool kFill>
+__global__ void __launch_bounds__(256)
+bases_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __restrict__ seg_off, int64_t first,
+                  int64_t nseg, int32_t n_ref, uint32_t flag_filter, int32_t min_mapq, SegRes* __restrict__ res,
+                  SegBases* __restrict__ resb, const int64_t* __restrict__ out_off,
+                  const SegBases* __restrict__ arena, int64_t w_base, int32_t* __restrict__ tid,
+                  int32_t* __restrict__ pos, int32_t* __restrict__ l_seq, int64_t* __restrict__ cig_off,
+                  int64_t* __restrict__ seq_off, int64_t* __restrict__ qual_off, int64_t* __restrict__ src) {
+    const int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nseg) return;
+    int64_t q = seg_off[i];
+    const int64_t end = seg_off[i + 1];
+    int64_t records = 0, mapped = 0, taken = 0, err_at = 0;
+    SegBases c = {0, 0, 0, 0, 0, 0};
+    int32_t err = 0;
+    int64_t w = 0, w_end = 0, cw = 0, sb = 0, qb = 0, cw_end = 0, sb_end = 0, qb_end = 0;
+    if (kFill) {
+        w = out_off[i];
+        w_end = w + res[i].kept;
+        const SegBases a = arena[i];          // words / seq_bytes / qual_bytes: this segment's arena starts
+        cw = a.words;
+        sb = a.seq_bytes;
+        qb = a.qual_bytes;
+        cw_end = cw + resb[i].words;
+        sb_end = sb + resb[i].seq_bytes;
+        qb_end = qb + resb[i].qual_bytes;
+    }
+    while (q < end) {
+        if (q + 4 > n) {
+            err = kSegIncomplete;
+            break;
+        }
+        const int32_t bs = mc::gz::ld_i32(d + q);
+        if (bs < 32) {
+            err = kSegBadSize;
+            err_at = q;
+            break;
+        }
+        if (q + 4 + (int64_t)bs > n) {
+            err = kSegIncomplete;
+            break;
+        }
+        const uint8_t* r = d + q + 4;
+        mc::gz::RecBases rb;
+        const int rc = mc::gz::rec_bases(r, r + bs, n_ref, flag_filter, min_mapq, rb);
+        if (rc == mc::gz::kRbMalformed) {
+            err = kSegMalformed;
+            err_at = q;
+            break;
+        }
+        q += 4 + (int64_t)bs;
+        ++records;
+        mapped += rb.mapped ? 1 : 0;
+        if (rc == mc::gz::kRbDropped) continue;
+        ++c.passed;
+        if (rc == mc::gz::kRbNoSeq) {
+            ++c.no_seq;
+            continue;
+        }
+        if (rc == mc::gz::kRbBadCigar) {
+            ++c.bad_cigar;
+            continue;
+        }
+        const int64_t nb = ((int64_t)rb.l_seq + 1) / 2;
+        const int64_t al = (nb + 3) & ~(int64_t)3;
+        ++taken;
+        c.words += rb.n_cigar;
+        c.seq_bytes += al;
+        c.qual_bytes += rb.l_seq;
+        if (kFill && w < w_end && cw + rb.n_cigar <= cw_end && sb + al <= sb_end && qb + rb.l_seq <= qb_end) {
+            tid[w] = rb.tid;
+            pos[w] = rb.pos;
+            l_seq[w] = rb.l_seq;
+            int64_t* s = src + 3 * (w - w_base);
+            s[0] = rb.cig - d;
+            s[1] = rb.seq - d;
+            s[2] = rb.qual - d;
+            cw += rb.n_cigar;
+            sb += al;
+            qb += rb.l_seq;
+            cig_off[w + 1] = cw;
+            seq_off[w + 1] = sb;
+            qual_off[w + 1] = qb;
+            ++w;
+        }
+    }
+    if (!kFill) {
+        SegRes s;
+        s.landing = q;
+        s.records = records;
+        s.mapped = mapped;
+        s.kept = taken;
+        s.err_at = err_at;
+        s.bytes = 0;
+        s.err = err;
+        s.pad = 0;
+        res[i] = s;
+        resb[i] = c;
+    }
+}
+
+// The payload of reads [w0, w0 + count) of the bases table, from the inflated
+// stream d[0, n) into the three arenas.  kGatherLanes lanes per read;
+// consecutive lanes write consecutive dwords of the destination, each dword
+// assembled from source bytes (the source is byte-aligned).  The lengths are
+// the destination ranges' own (cig_off / seq_off / qual_off, written by the
+// fill walk inside the arena sizes of the count pass) and every range is
+// checked against the arenas and the stream before a byte moves.  QUAL is
+// packed, so a read's qualities start at any byte: up to 3 leading and 3
+// trailing bytes go out as bytes, the aligned middle as dwords.
+constexpr int kGatherLanes = 16;
+
+__global__ void __launch_bounds__(256)
+bases_gather_kernel(const uint8_t* __restrict__ d, int64_t n, int64_t w0, int64_t count,
+                    const int64_t* __restrict__ src, const int32_t* __restrict__ l_seq,
+                    const int64_t* __restrict__ cig_off, const int64_t* __restrict__ seq_off,
+                    const int64_t* __restrict__ qual_off, uint32_t* __restrict__ cigar, int64_t n_words,
+                    uint8_t* __restrict__ seq, int64_t seq_bytes, uint8_t* __restrict__ qual, int64_t qual_bytes) {
+    const int gl = threadIdx.x % kGatherLanes;
+    const int64_t k = (int64_t)blockIdx.x * (256 / kGatherLanes) + threadIdx.x / kGatherLanes;
+    if (k >= count) return;
+    const int64_t w = w0 + k;
+    const int64_t l = l_seq[w];
+    const int64_t c0 = cig_off[w], c1 = cig_off[w + 1];
+    const int64_t s0 = seq_off[w], s1 = seq_off[w + 1];
+    const int64_t q0 = qual_off[w], q1 = qual_off[w + 1];
+    const int64_t a_cig = src[3 * k], a_seq = src[3 * k + 1], a_qual = src[3 * k + 2];
+    const int64_t nb = (l + 1) / 2;
+    const bool ok = l > 0 && c0 >= 0 && c1 >= c0 && c1 <= n_words && a_cig >= 0 && a_cig + 4 * (c1 - c0) <= n &&
+                    s0 >= 0 && (s0 & 3) == 0 && s1 - s0 == ((nb + 3) & ~(int64_t)3) && s1 <= seq_bytes &&
+                    a_seq >= 0 && a_seq + nb <= n && q0 >= 0 && q1 - q0 == l && q1 <= qual_bytes && a_qual >= 0 &&
+                    a_qual + l <= n;
+    if (!ok) return;
+    for (int64_t j = gl; j < c1 - c0; j += kGatherLanes) cigar[c0 + j] = mc::gz::ld_u32(d + a_cig + 4 * j);
+    {
+        const uint8_t* s = d + a_seq;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(seq + s0);
+        for (int64_t j = gl; j < (s1 - s0) >> 2; j += kGatherLanes) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * j + e < nb) v |= (uint32_t)s[4 * j + e] << (8 * e);
+            dst[j] = v;
+        }
+    }
+    {
+        const uint8_t* s = d + a_qual;
+        const int64_t head = min((int64_t)((4 - (q0 & 3)) & 3), l);
+        const int64_t body = (l - head) >> 2, tail = l - head - 4 * body;
+        if (gl < head) qual[q0 + gl] = s[gl];
+        uint32_t* dst = reinterpret_cast<uint32_t*>(qual + q0 + head);
+        for (int64_t j = gl; j < body; j += kGatherLanes) dst[j] = mc::gz::ld_u32(s + head + 4 * j);
+        if (gl < tail) qual[q0 + head + 4 * body + gl] = s[head + 4 * body + gl];
+    }
+}
+
 template <typename T>
 struct DBuf {
     T* p = nullptr;
@@ -600,6 +782,17 @@ struct mc_bam_gpu {
     DBuf<uint8_t> sseq;               // scan mode: packed nt16 bases
     DBuf<int64_t> boff;               // scan mode: per-segment byte offsets of the fill
     int64_t n_bytes = 0;
+    // bases mode (bases_walk_kernel + bases_gather_kernel): tid, pos and span (= l_seq) above, then
+    bool bases_mode = false;
+    int32_t min_mapq = 0;
+    DBuf<int64_t> bcig_off, bseq_off, bqual_off;   // [n_kept + 1] each, absolute into the arenas
+    DBuf<uint32_t> bcigar;                          // CIGAR words
+    DBuf<uint8_t> bqual;                            // qualities (the bases are in sseq)
+    int64_t n_words = 0, n_qual = 0;                // arena sizes (the bases': n_bytes)
+    int64_t b_passed = 0, b_no_seq = 0, b_bad_cigar = 0;
+    DBuf<SegBases> resb, barena;                    // per segment: the count pass, the fill's arena starts
+    DBuf<int64_t> bsrc;                             // per read of a window: 3 offsets into the inflated stream
+    PinnedBuf<SegBases> hresb;
     DBuf<uint8_t> comp[2], inflated, tail;   // comp: window k's compressed bytes in comp[k & 1]
     hipStream_t up_stream = nullptr;          // uploads of the next window (overlap the current one's kernels)
     hipStream_t kstream[3] = {};              // resident decode: inflate streams besides `stream`
@@ -848,6 +1041,83 @@ int sync_segments(mc_bam_gpu* g, int64_t o, int64_t n, int64_t i0, int64_t nseg,
     return MC_OK;
 }
 
+// Bases mode's fill of one parsed window: g->res / g->out_off hold the final
+// counts and read offsets of its nseg segments, g->hresb the host copy of the
+// second per-segment array; `total` reads join the table.  The arenas grow
+// here, so this is where a file whose reads do not fit in device memory fails.
+int fill_bases(mc_bam_gpu* g, int64_t n, int64_t nseg, int64_t total) {
+    hipStream_t st = g->stream;
+    const uint8_t* d = g->inflated.p;
+    SegBases* B = g->hresb.p;
+    // arena starts per segment (absolute), then the sizes go back up as the bounds of the fill
+    std::vector<SegBases> start(nseg);
+    int64_t words = 0, sbytes = 0, qbytes = 0, passed = 0, no_seq = 0, bad_cigar = 0;
+    for (int64_t i = 0; i < nseg; ++i) {
+        start[i] = SegBases{0, 0, 0, g->n_words + words, g->n_bytes + sbytes, g->n_qual + qbytes};
+        words += B[i].words;
+        sbytes += B[i].seq_bytes;
+        qbytes += B[i].qual_bytes;
+        passed += B[i].passed;
+        no_seq += B[i].no_seq;
+        bad_cigar += B[i].bad_cigar;
+    }
+    const size_t need = (size_t)(g->n_kept + total) + 4;
+    auto grow = [&](auto& buf, size_t elems, size_t keep) -> int {
+        if (buf.reserve(elems, st, keep) != hipSuccess) {
+            (void)hipGetLastError();
+            mc::set_error("%s: the decoded reads do not fit in device memory (%lld reads, %lld bases so far)",
+                          g->path.c_str(), (long long)(g->n_kept + total), (long long)(g->n_qual + qbytes));
+            return MC_E_HIP;
+        }
+        return MC_OK;
+    };
+    const size_t have = (size_t)g->n_kept;
+    if (int rc = grow(g->tid, need, have)) return rc;
+    if (int rc = grow(g->pos, need, have)) return rc;
+    if (int rc = grow(g->span, need, have)) return rc;
+    if (int rc = grow(g->bcig_off, need + 1, have + 1)) return rc;
+    if (int rc = grow(g->bseq_off, need + 1, have + 1)) return rc;
+    if (int rc = grow(g->bqual_off, need + 1, have + 1)) return rc;
+    if (int rc = grow(g->bcigar, (size_t)(g->n_words + words) + 4, (size_t)g->n_words)) return rc;
+    if (int rc = grow(g->sseq, (size_t)(g->n_bytes + sbytes) + 16, (size_t)g->n_bytes)) return rc;
+    if (int rc = grow(g->bqual, (size_t)(g->n_qual + qbytes) + 16, (size_t)g->n_qual)) return rc;
+    if (int rc = grow(g->bsrc, 3 * (size_t)total + 4, 0)) return rc;
+    if (g->n_kept == 0) {
+        HIP_TRY(hipMemsetAsync(g->bcig_off.p, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(g->bseq_off.p, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(g->bqual_off.p, 0, 8, st));
+    }
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(g->resb.p, B, nseg * sizeof(SegBases), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g->barena.p, start.data(), nseg * sizeof(SegBases), hipMemcpyHostToDevice, st));
+        // (a read the fill skipped keeps these negative source offsets, and the gather refuses it)
+        HIP_TRY(hipMemsetAsync(g->bsrc.p, 0xFF, 3 * (size_t)total * 8, st));
+        const int grid = (int)((nseg + 255) / 256);
+        bases_walk_kernel<true><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, 0, nseg, (int32_t)g->hdr.names.size(),
+                                                      g->flag_filter, g->min_mapq, g->res.p, g->resb.p, g->out_off.p,
+                                                      g->barena.p, g->n_kept, g->tid.p, g->pos.p, g->span.p,
+                                                      g->bcig_off.p, g->bseq_off.p, g->bqual_off.p, g->bsrc.p);
+        HIP_TRY(hipGetLastError());
+        constexpr int per_block = 256 / kGatherLanes;
+        const int64_t blocks = (total + per_block - 1) / per_block;
+        MC_REQUIRE(blocks < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^35 reads in one window");
+        bases_gather_kernel<<<(unsigned)blocks, 256, 0, st>>>(d, n, g->n_kept, total, g->bsrc.p, g->span.p,
+                                                             g->bcig_off.p, g->bseq_off.p, g->bqual_off.p,
+                                                             g->bcigar.p, g->n_words + words, g->sseq.p,
+                                                             g->n_bytes + sbytes, g->bqual.p, g->n_qual + qbytes);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (start[] and the pinned counts are free again)
+    g->n_kept += total;
+    g->n_words += words;
+    g->n_bytes += sbytes;
+    g->n_qual += qbytes;
+    g->b_passed += passed;
+    g->b_no_seq += no_seq;
+    g->b_bad_cigar += bad_cigar;
+    return MC_OK;
+}
+
 // Parses the records in inflated[o, n); partial: the window is not the
 // file's last, so an incomplete last record is carried (*consumed = its
 // offset).  Appends kept intervals to g->tid/pos/span; base: the stream
@@ -863,6 +1133,11 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     HIP_TRY(g->res.reserve(nseg));
     HIP_TRY(g->h64.reserve(2 * (nseg + 1)));   // (scan mode: the byte offsets after the record offsets)
     HIP_TRY(g->hres.reserve(nseg));
+    if (g->bases_mode) {
+        HIP_TRY(g->resb.reserve(nseg));
+        HIP_TRY(g->barena.reserve(nseg));
+        HIP_TRY(g->hresb.reserve(nseg));
+    }
     int64_t* h = g->h64.p;
     std::vector<int64_t> seg(nseg + 1, n);
     seg[0] = o;
@@ -886,7 +1161,12 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
         std::memcpy(h, seg.data() + first, (nseg + 1 - first) * 8);
         HIP_TRY(hipMemcpyAsync(g->seg_off.p + first, h, (nseg + 1 - first) * 8, hipMemcpyHostToDevice, st));
         const int grid = (int)((nseg - first + 255) / 256);
-        if (g->scan_mode)
+        if (g->bases_mode)
+            bases_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->flag_filter,
+                                                           g->min_mapq, g->res.p, g->resb.p, nullptr, nullptr, 0,
+                                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                           nullptr);
+        else if (g->scan_mode)
             scan_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->res.p, nullptr,
                                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                                           nullptr, nullptr);
@@ -958,6 +1238,13 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
             break;
         }
     }
+    // bases mode: every segment's last count pass (the rounds re-walk only segments they moved)
+    SegBases* B = g->hresb.p;
+    const SegBases kNoBases = {0, 0, 0, 0, 0, 0};
+    if (g->bases_mode) {
+        HIP_TRY(hipMemcpyAsync(B, g->resb.p, nseg * sizeof(SegBases), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     // segments after an incomplete stop are empty; their results may be stale
     int64_t total = 0, records = 0, mapped = 0, tail = n, bytes = 0;
     std::vector<int64_t> koff(nseg + 1), bo(nseg + 1);
@@ -965,6 +1252,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
         SegRes& r = R[i];
         if (seg[i] >= seg[i + 1] && seg[i] == n) {   // empty tail segment
             r.kept = r.records = r.mapped = r.bytes = 0;
+            if (g->bases_mode) B[i] = kNoBases;
         }
         koff[i] = g->n_kept + total;
         bo[i] = g->n_bytes + bytes;
@@ -978,6 +1266,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
                 koff[j] = g->n_kept + total;
                 bo[j] = g->n_bytes + bytes;
                 R[j].kept = R[j].records = R[j].mapped = R[j].bytes = 0;
+                if (g->bases_mode) B[j] = kNoBases;
             }
             break;
         }
@@ -988,6 +1277,13 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     std::memcpy(h, koff.data(), nseg * 8);
     HIP_TRY(hipMemcpyAsync(g->out_off.p, h, nseg * 8, hipMemcpyHostToDevice, st));
     const size_t need = (size_t)(g->n_kept + total) + 4;
+    if (g->bases_mode) {
+        if (int rc = fill_bases(g, n, nseg, total)) return rc;
+        g->hdr.n_records += records;
+        g->hdr.n_mapped += mapped;
+        g->hdr.n_unmapped += records - mapped;
+        return MC_OK;
+    }
     HIP_TRY(g->tid.reserve(need, st, g->n_kept));
     HIP_TRY(g->pos.reserve(need, st, g->n_kept));
     HIP_TRY(g->span.reserve(need, st, g->n_kept));
@@ -1447,7 +1743,7 @@ int inflate_resident(mc_bam_gpu* g, int fd, const VMap* vm, size_t vsize, const 
 
 // The per-contig table of the record walk, zeroed (n_ref + 1 entries).
 int init_ext(mc_bam_gpu* g) {
-    if (g->scan_mode || g->reads_mode) return MC_OK;   // (no extents table)
+    if (g->scan_mode || g->reads_mode || g->bases_mode) return MC_OK;   // (no extents table)
     const size_t m = g->hdr.names.size() + 1;
     HIP_TRY(g->ext.reserve(m));
     HIP_TRY(hipMemsetAsync(g->ext.p, 0, m * sizeof(ExtAcc), g->stream));
@@ -1527,7 +1823,8 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
         size_t free_b = 0, tot_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &tot_b));
         if (bg.t.joinable()) free_b += g->comp[0].cap;
-        if (resident_fits(mf.size, total, blocks.size(), max_lanes, free_b)) {
+        // (bases mode copies nearly every inflated byte into its arenas: as much again)
+        if (resident_fits(mf.size, total, blocks.size(), max_lanes, free_b, g->bases_mode ? total : 0)) {
             const int rc = gpu_decode_resident(g, mf, blocks, total, max_lanes, bg.t.joinable() ? &bg : nullptr);
             if (rc == MC_OK && bg.t.joinable()) {
                 if (int urc = bg.join()) return urc;
@@ -2103,6 +2400,88 @@ extern "C" int mc_bam_gpu_reads_copy(const mc_bam_gpu* g, int32_t* tid, int32_t*
     return MC_OK;
 }
 
+extern "C" int mc_bam_gpu_open_bases(const char* path, int device, int n_threads, uint32_t flag_filter, int min_mapq,
+                                     int64_t window_bytes, mc_bam_gpu** out) {
+    MC_REQUIRE(path && out, MC_E_INVALID, "null argument");
+    *out = nullptr;
+    MC_REQUIRE(min_mapq >= 0 && min_mapq <= 255, MC_E_INVALID, "min_mapq %d outside 0..255", min_mapq);
+    std::unique_ptr<mc_bam_gpu> g;
+    if (int rc = open_common(path, device, n_threads, flag_filter, g)) return rc;
+    g->bases_mode = true;
+    g->min_mapq = min_mapq;
+    const double t0 = now_s();
+    if (int rc = gpu_decode(g.get(), window_bytes)) return rc;
+    g->t_open = (now_s() - t0) * 1e3;
+    *out = g.release();
+    return MC_OK;
+}
+
+extern "C" int mc_bam_gpu_bases_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_tid, const int32_t** d_pos,
+                                       const int64_t** d_cig_off, const uint32_t** d_cigar, int64_t* n_words,
+                                       const int32_t** d_l_seq, const int64_t** d_seq_off, const uint8_t** d_seq,
+                                       int64_t* seq_bytes, const int64_t** d_qual_off, const uint8_t** d_qual,
+                                       int64_t* qual_bytes) {
+    MC_REQUIRE(g && n && d_tid && d_pos && d_cig_off && d_cigar && n_words && d_l_seq && d_seq_off && d_seq &&
+                   seq_bytes && d_qual_off && d_qual && qual_bytes,
+               MC_E_INVALID, "null argument");
+    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    *n = g->n_kept;
+    *d_tid = g->tid.p;
+    *d_pos = g->pos.p;
+    *d_cig_off = g->bcig_off.p;
+    *d_cigar = g->bcigar.p;
+    *n_words = g->n_words;
+    *d_l_seq = g->span.p;
+    *d_seq_off = g->bseq_off.p;
+    *d_seq = g->sseq.p;
+    *seq_bytes = g->n_bytes;
+    *d_qual_off = g->bqual_off.p;
+    *d_qual = g->bqual.p;
+    *qual_bytes = g->n_qual;
+    return MC_OK;
+}
+
+extern "C" int mc_bam_gpu_bases_copy(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int64_t* cig_off,
+                                     uint32_t* cigar, int32_t* l_seq, int64_t* seq_off, uint8_t* seq,
+                                     int64_t* qual_off, uint8_t* qual) {
+    MC_REQUIRE(g && cig_off && seq_off && qual_off, MC_E_INVALID, "null argument");
+    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(((tid && pos && l_seq) || !g->n_kept) && (cigar || !g->n_words) && (seq || !g->n_bytes) &&
+                   (qual || !g->n_qual),
+               MC_E_INVALID, "null argument");   // (an empty table: only the offsets' first entries)
+    HIP_TRY(hipSetDevice(g->device));
+    const size_t n = (size_t)g->n_kept;
+    hipStream_t st = g->stream;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(tid, g->tid.p, n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(pos, g->pos.p, n * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(l_seq, g->span.p, n * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (g->bcig_off.p) {
+        HIP_TRY(hipMemcpyAsync(cig_off, g->bcig_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(seq_off, g->bseq_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(qual_off, g->bqual_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, st));
+    } else {   // (a file without a record window: nothing was allocated)
+        cig_off[0] = seq_off[0] = qual_off[0] = 0;
+    }
+    if (g->n_words) HIP_TRY(hipMemcpyAsync(cigar, g->bcigar.p, (size_t)g->n_words * 4, hipMemcpyDeviceToHost, st));
+    if (g->n_bytes) HIP_TRY(hipMemcpyAsync(seq, g->sseq.p, (size_t)g->n_bytes, hipMemcpyDeviceToHost, st));
+    if (g->n_qual) HIP_TRY(hipMemcpyAsync(qual, g->bqual.p, (size_t)g->n_qual, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MC_OK;
+}
+
+extern "C" int mc_bam_gpu_bases_counts(const mc_bam_gpu* g, int64_t* records, int64_t* kept, int64_t* no_seq,
+                                       int64_t* bad_cigar) {
+    MC_REQUIRE(g && records && kept && no_seq && bad_cigar, MC_E_INVALID, "null argument");
+    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    *records = g->hdr.n_records;
+    *kept = g->b_passed;
+    *no_seq = g->b_no_seq;
+    *bad_cigar = g->b_bad_cigar;
+    return MC_OK;
+}
+
 extern "C" int mc_bam_gpu_header(const mc_bam_gpu* g, const mc_bam** header) {
     MC_REQUIRE(g && header, MC_E_INVALID, "null argument");
     *header = &g->hdr;
@@ -2112,6 +2491,7 @@ extern "C" int mc_bam_gpu_header(const mc_bam_gpu* g, const mc_bam** header) {
 extern "C" int mc_bam_gpu_intervals_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_tid,
                                            const int32_t** d_pos, const int32_t** d_span) {
     MC_REQUIRE(g && n && d_tid && d_pos && d_span, MC_E_INVALID, "null argument");
+    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     *n = g->n_kept;
     *d_tid = g->tid.p;
     *d_pos = g->pos.p;
@@ -2121,6 +2501,7 @@ extern "C" int mc_bam_gpu_intervals_device(const mc_bam_gpu* g, int64_t* n, cons
 
 extern "C" int mc_bam_gpu_intervals(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int32_t* span) {
     MC_REQUIRE(g && tid && pos && span, MC_E_INVALID, "null argument");
+    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     HIP_TRY(hipSetDevice(g->device));
     if (g->n_kept) {
         HIP_TRY(hipMemcpy(tid, g->tid.p, g->n_kept * 4, hipMemcpyDeviceToHost));
@@ -2181,6 +2562,9 @@ extern "C" int mc_bam_gpu_trim(mc_bam_gpu* g, int64_t* freed) {
     drop(g->out_off);
     drop(g->res);
     drop(g->boff);
+    drop(g->resb);
+    drop(g->barena);
+    drop(g->bsrc);
     if (freed) *freed = bytes;
     return MC_OK;
 }
@@ -2224,6 +2608,7 @@ extern "C" int mc_bam_gpu_open_contigs(const char* path, const char* bai_path, i
 
 extern "C" int mc_bam_gpu_extents(const mc_bam_gpu* g, int32_t n_ref, mc_contig_extent* ext, int64_t* n_no_coor) {
     MC_REQUIRE(g && (ext || n_ref == 0) && n_no_coor, MC_E_INVALID, "null argument");
+    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     MC_REQUIRE(n_ref == (int32_t)g->hdr.names.size(), MC_E_INVALID, "the file has %zu contigs, not %d",
                g->hdr.names.size(), n_ref);
     HIP_TRY(hipSetDevice(g->device));
@@ -2330,6 +2715,7 @@ extern "C" int mc_bam_gpu_restrict(mc_bam_gpu* g, int32_t n_sel, const int32_t* 
 extern "C" int mc_bam_gpu_intervals_range(const mc_bam_gpu* g, int64_t first, int64_t count, int32_t* tid,
                                           int32_t* pos, int32_t* span) {
     MC_REQUIRE(g && tid && pos && span, MC_E_INVALID, "null argument");
+    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     MC_REQUIRE(first >= 0 && count >= 0 && first + count <= g->n_kept, MC_E_RANGE,
                "intervals [%lld, %lld) outside the %lld kept", (long long)first, (long long)(first + count),
                (long long)g->n_kept);
@@ -2446,6 +2832,27 @@ extern "C" int mc_bgzf_scan_host(const char* path, int n_threads, int64_t* n_blo
 extern "C" int mc_bam_rec_chain_host(const uint8_t* d, int64_t n, int64_t q, int32_t n_ref, int chain) {
     MC_REQUIRE(d && n >= 0 && q >= 0 && chain >= 1, MC_E_INVALID, "bad argument");
     return mc::gz::rec_chain(d, q, n, n_ref, chain) ? 1 : 0;
+}
+
+// rec_bases on the host for one record body (unit tests): the class, and for a
+// record taken out7 = tid, pos, l_seq, the CIGAR word count and the offsets in
+// r of the CIGAR words, SEQ and QUAL
+extern "C" int mc_bam_rec_bases_host(const uint8_t* r, int64_t len, int32_t n_ref, uint32_t flag_filter,
+                                     int32_t min_mapq, int64_t* out7) {
+    MC_REQUIRE(r && out7 && len >= 0, MC_E_INVALID, "bad argument");
+    mc::gz::RecBases rb{};
+    const int rc = mc::gz::rec_bases(r, r + len, n_ref, flag_filter, min_mapq, rb);
+    for (int i = 0; i < 7; ++i) out7[i] = 0;
+    if (rc == mc::gz::kRbTaken) {
+        out7[0] = rb.tid;
+        out7[1] = rb.pos;
+        out7[2] = rb.l_seq;
+        out7[3] = rb.n_cigar;
+        out7[4] = rb.cig - r;
+        out7[5] = rb.seq - r;
+        out7[6] = rb.qual - r;
+    }
+    return rc;
 }
 
 // rec_parse on the host for one record body (unit tests)

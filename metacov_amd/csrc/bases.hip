@@ -37,6 +37,11 @@
 //                         with plain load-add-store: a tile has one owner in
 //                         a launch and the launches of successive batches
 //                         are ordered on the stream.  No global atomics.
+//   bases_ends_kernel     mc_bases_add_batch_device only (the batch is in
+//                         device memory, e.g. the GPU decoder's bases-mode
+//                         table): one thread writes the first and last read's
+//                         (tid, pos) behind the pre-pass flags, so the words
+//                         the host needs come back in the same small copy.
 //   sites_count / scan / emit   the count - scan - emit pattern of runs.hip
 //                         over the planes with the site predicate; the host
 //                         reads the total (8 bytes) between scan and emit.
@@ -580,10 +585,12 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
 namespace {
 
 // Why read i of the batch is invalid, for mc_last_error (the pre-pass found i).
+// label (>= 0): the read's index in the caller's batch, where the arrays are
+// an excerpt of it (mc_bases_add_batch_device copies back two reads).
 void name_bad_read(const mc_bases* h, int64_t i, const int32_t* tid, const int32_t* pos, const int64_t* cig_off,
                    const uint32_t* cigar, const int32_t* l_seq, const int64_t* seq_off, const int64_t* qual_off,
-                   int64_t n_words, int64_t seq_bytes, int64_t qual_bytes) {
-    const long long r = (long long)i;
+                   int64_t n_words, int64_t seq_bytes, int64_t qual_bytes, int64_t label = -1) {
+    const long long r = (long long)(label >= 0 ? label : i);
     if (tid[i] < 0 || tid[i] >= h->n_ref) return mc::set_error("read %lld: tid %d out of range", r, tid[i]);
     if (pos[i] < 0) return mc::set_error("read %lld: negative pos %d", r, pos[i]);
     if (l_seq[i] < 0) return mc::set_error("read %lld: negative l_seq %d", r, l_seq[i]);
@@ -696,6 +703,124 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     h->have_last = true;
     h->last_tid = tid[n - 1];
     h->last_pos = pos[n - 1];
+    h->n_reads += n;
+    h->have_sites = false;
+    return MC_OK;
+}
+
+namespace {
+
+// ends[0..3] = the first and the last read's (tid, pos): the few words of a
+// device batch the host needs (tile range, order across batches).
+__global__ void bases_ends_kernel(Batch b, int32_t* __restrict__ ends) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        ends[0] = b.tid[0];
+        ends[1] = b.pos[0];
+        ends[2] = b.tid[b.n - 1];
+        ends[3] = b.pos[b.n - 1];
+    }
+}
+
+}  // namespace
+
+extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                                         const int64_t* d_cig_off, const uint32_t* d_cigar, int64_t n_words,
+                                         const int32_t* d_l_seq, const int64_t* d_seq_off, const uint8_t* d_seq,
+                                         int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
+                                         int64_t qual_bytes) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
+    if (n == 0) return MC_OK;
+    MC_REQUIRE(d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off, MC_E_INVALID, "null read arrays");
+    MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
+    MC_REQUIRE((n_words == 0 || d_cigar) && (seq_bytes == 0 || d_seq) && (qual_bytes == 0 || d_qual), MC_E_INVALID,
+               "null arena");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->span.reserve((size_t)n));
+    hipStream_t st = h->stream;
+    h->pin[0] = kNoBad;
+    h->pin[1] = 0;
+    HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
+    Batch b{d_tid, d_pos, d_l_seq, d_cig_off, d_cigar, d_seq_off, d_seq, d_qual_off, d_qual,
+            n, n_words, seq_bytes, qual_bytes};
+    const int64_t groups = (n + kThreads - 1) / kThreads;
+    MC_REQUIRE(groups < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^39 reads in one batch");
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(bases_prepass_kernel, dim3((unsigned)groups), dim3(kThreads), 0, st, b, h->n_ref, h->span.p,
+                       h->flags.p, reinterpret_cast<int32_t*>(h->flags.p + 1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    // flags[2..3] (the handle's flags buffer has room for 256 words): the ends, one copy with the flags
+    hipLaunchKernelGGL(bases_ends_kernel, dim3(1), dim3(64), 0, st, b, reinterpret_cast<int32_t*>(h->flags.p + 2));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->pin, h->flags.p, 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int32_t ends[4];
+    std::memcpy(ends, &h->pin[2], 16);
+    if (h->have_last && ends[0] >= 0 && ends[1] >= 0)
+        MC_REQUIRE(h->last_tid < ends[0] || (h->last_tid == ends[0] && h->last_pos <= ends[1]), MC_E_INVALID,
+                   "read 0: reads are not sorted by (tid, pos) against the previous batch");
+    const unsigned long long bad = h->pin[0];
+    if (bad != kNoBad) {
+        if (bad >= (unsigned long long)n) {
+            mc::set_error("read index %llu out of range", bad);
+            return MC_E_INVALID;
+        }
+        // the bad read's fields behind its predecessor's key (two-entry arrays: name_bad_read's i - 1 and i)
+        const int64_t i = (int64_t)bad, j = i > 0 ? 1 : 0;
+        int32_t t2[2] = {0, 0}, p2[2] = {0, 0}, l2[2] = {0, 0};
+        int64_t c3[3] = {0, 0, 0}, s2[2] = {0, 0}, q2[2] = {0, 0};
+        const auto down = [st](void* d, const void* s, size_t bytes) {
+            return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, st);
+        };
+        HIP_TRY(down(t2, d_tid + i - j, (size_t)(j + 1) * 4));
+        HIP_TRY(down(p2, d_pos + i - j, (size_t)(j + 1) * 4));
+        HIP_TRY(down(l2 + j, d_l_seq + i, 4));
+        HIP_TRY(down(c3 + j, d_cig_off + i, 16));
+        HIP_TRY(down(s2 + j, d_seq_off + i, 8));
+        HIP_TRY(down(q2 + j, d_qual_off + i, 8));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::vector<uint32_t> words;
+        int64_t local_words = n_words;
+        if (c3[j] >= 0 && c3[j + 1] >= c3[j] && c3[j + 1] <= n_words) {   // the words, rebased to offset 0
+            words.resize((size_t)(c3[j + 1] - c3[j]));
+            if (!words.empty()) {
+                HIP_TRY(down(words.data(), d_cigar + c3[j], words.size() * 4));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            // (the bases' and qualities' offsets stay absolute: name_bad_read only compares them)
+            c3[j + 1] -= c3[j];
+            c3[j] = 0;
+            local_words = c3[j + 1];
+        }
+        name_bad_read(h, j, t2, p2, c3, words.data(), l2, s2, q2, local_words, seq_bytes, qual_bytes, i);
+        return MC_E_INVALID;
+    }
+    int32_t max_span = 0;
+    std::memcpy(&max_span, &h->pin[1], 4);
+    MC_REQUIRE(max_span >= 0, MC_E_STATE, "maximum span %d out of range", max_span);
+    HIP_TRY(hipEventRecord(h->ev[2], st));
+    const auto t_lo = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
+                                       std::make_pair(ends[0], (int64_t)ends[1] - kTile));
+    const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
+                                       std::make_pair(ends[2], (int64_t)ends[3] + max_span));
+    if (max_span > 0 && t_lo < t_hi) {
+        hipLaunchKernelGGL(bases_pileup_kernel, dim3((unsigned)(t_hi - t_lo)), dim3(kThreads), 0, st, b, h->span.p,
+                           h->tiles.p, h->order.p + (t_lo - h->tile_key.begin()), max_span, h->min_baseq,
+                           h->planes.p, h->stride);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays are free again
+    float a = 0, c = 0;
+    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+    h->ms_prepass += a;
+    h->ms_pileup += c;
+    h->have_last = true;
+    h->last_tid = ends[2];
+    h->last_pos = ends[3];
     h->n_reads += n;
     h->have_sites = false;
     return MC_OK;

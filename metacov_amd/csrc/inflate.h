@@ -820,6 +820,70 @@ MC_HD int rec_parse(const uint8_t* r, const uint8_t* rend, int32_t n_ref, uint32
     return 1;
 }
 
+// The base counter's record rule (bases_src.cpp's next_batch) for one record
+// body r[0, rend - r) after block_size.  Every record is checked first
+// (kRbMalformed: l_seq < 0, a CIGAR, SEQ or QUAL that runs past the record, a
+// tid outside [-1, n_ref), a body shorter than its fixed fields); a record
+// with tid < 0, a flag in flag_filter or mapq < min_mapq is kRbDropped; a kept
+// one without SEQ is kRbNoSeq; one whose CIGAR query length (the CG:B,I tag
+// resolved as rec_parse resolves it) differs from l_seq is kRbBadCigar; the
+// rest is kRbTaken with its fields and the addresses of its CIGAR words
+// (n_cigar of them), packed bases and qualities, all inside [r, rend).
+// Reads nothing outside [r, rend), whatever the bytes are.
+enum : int { kRbDropped = 0, kRbTaken = 1, kRbNoSeq = 2, kRbBadCigar = 3, kRbMalformed = 4 };
+
+struct RecBases {
+    int32_t tid, pos, l_seq;
+    uint32_t n_cigar;
+    const uint8_t* cig;
+    const uint8_t* seq;
+    const uint8_t* qual;
+    bool mapped;
+};
+
+MC_HD int rec_bases(const uint8_t* r, const uint8_t* rend, int32_t n_ref, uint32_t flag_filter, int32_t min_mapq,
+                    RecBases& out) {
+    out.mapped = false;
+    if (rend - r < 32) return kRbMalformed;
+    const uint64_t bs = (uint64_t)(rend - r);
+    const int32_t tid = ld_i32(r);
+    const uint32_t l_name = r[8], mapq = r[9], flag = ld_u16(r + 14);
+    uint32_t n_cigar = ld_u16(r + 12);
+    const int32_t l_seq = ld_i32(r + 16);
+    if (l_seq < 0 || tid < -1 || tid >= n_ref) return kRbMalformed;
+    const uint64_t seq_at = 32ull + l_name + 4ull * n_cigar;
+    const uint64_t nbytes = ((uint64_t)l_seq + 1) / 2;
+    if (seq_at + nbytes + (uint64_t)l_seq > bs) return kRbMalformed;
+    out.mapped = tid >= 0 && !(flag & 4u);
+    if (tid < 0 || (flag & flag_filter) || (int32_t)mapq < min_mapq) return kRbDropped;
+    if (l_seq == 0) return kRbNoSeq;
+    const uint8_t* cig = r + 32 + l_name;
+    const uint8_t* seq = r + seq_at;
+    if (n_cigar == 2 && ld_u32(cig) == (((uint32_t)l_seq << 4) | 4u) && (ld_u32(cig + 4) & 0xFu) == 3u) {
+        const uint8_t* aux = seq + nbytes + (uint64_t)l_seq;   // <= rend (checked above)
+        const uint8_t* words = nullptr;
+        uint32_t cnt = 0;
+        if (find_cg(aux, rend, &words, &cnt) && words) {
+            cig = words;
+            n_cigar = cnt;
+        }
+    }
+    int64_t qlen = 0;
+    for (uint32_t k = 0; k < n_cigar; ++k) {
+        const uint32_t cw = ld_u32(cig + 4ull * k);
+        if ((0x193u >> (cw & 0xFu)) & 1u) qlen += cw >> 4;
+    }
+    if (qlen != l_seq) return kRbBadCigar;
+    out.tid = tid;
+    out.pos = ld_i32(r + 4);
+    out.l_seq = l_seq;
+    out.n_cigar = n_cigar;
+    out.cig = cig;
+    out.seq = seq;
+    out.qual = seq + nbytes;
+    return kRbTaken;
+}
+
 #undef MC_HD
 
 }  // namespace gz
