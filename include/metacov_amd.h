@@ -433,7 +433,7 @@ int mc_windows_dims(int32_t* tile, int32_t* min_window, int32_t* max_bins, int32
  * [site_first[s], site_first[s + 1]); site i is at site_pos[i] (relative to
  * the contig, ascending within a segment) with the six counts
  * site_counts[i][0..5].  Results stay in device memory owned by the handle
- * (buffers only grow) until the next mc_bases_sites, _add_batch or _begin.
+ * (buffers only grow) until the next mc_bases_sites, _add_batch, _set or _begin.
  * mc_bases_timing: HIP-event times since begin of the pre-pass and pileup
  * kernels (summed over the batches) and of the last sites call, the tile
  * count and the reads added.  mc_bases_dims (test hook): the tile size.
@@ -492,6 +492,70 @@ int mc_bases_sites_get(const mc_bases* h, int64_t first, int64_t count, int64_t*
 int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pileup_ms, float* sites_ms, int64_t* tiles,
                     int64_t* reads);
 int mc_bases_dims(int32_t* tile);
+
+/* Consensus (mc_bases_consensus), a third stage over the planes on the device:
+ * one letter per position, called from the counts alone.  A consensus built
+ * here never contains inserted bases (the planes hold none); insertion
+ * alleles are out of scope.  Integer only, exact and deterministic.
+ *
+ * At plane index i let a[0..3] be the A, C, G, T counts, d the DEL count (the
+ * N plane is ignored, as in sites), depth = a0 + a1 + a2 + a3 + d in 64 bits
+ * and r the reference code where ref is given (uint8 [N], exactly as
+ * mc_bases_sites takes it: 0..3 = A/C/G/T, anything else = unknown).
+ * qualifies(x) means x >= max(min_count, 1) and x * 10^6 >= call_ppm * depth,
+ * in 64-bit integers.  Every position falls into exactly one class:
+ *   LOW     depth < max(min_depth, 1).  Letter N; with MC_CONS_FILL_REF and r
+ *           known, the reference base in lower case (acgt).
+ *   otherwise top is the first maximum of (A, C, G, T, DEL) in channel order:
+ *           a base wins a tie against DEL, a lower channel a tie between bases.
+ *   DEL     top is DEL and qualifies(d).  Letter '-' in the aligned output,
+ *           nothing in the compact one.  top is DEL and does not qualify:
+ *           NOCALL, letter N.
+ *   top is a base, without MC_CONS_IUPAC: CALLED with top's letter if it
+ *           qualifies, else NOCALL (N).
+ *   top is a base, with MC_CONS_IUPAC: Q = the bases b with qualifies(a[b]).
+ *           Empty: NOCALL.  One element (it is top, qualifies being monotone in
+ *           the count): CALLED.  Two to four: AMBIG with the IUPAC letter of the
+ *           set, ".ACMGRSVTWYHKDBN"[mask] with bit A = 1, C = 2, G = 4, T = 8.
+ * Two outputs: the aligned sequence has one letter per position (indices are
+ * plane indices, segment s owns [seg_off[s], seg_off[s + 1])); the compact
+ * sequence is the aligned one without its '-', segment s owning
+ * [out_first[s], out_first[s + 1]), *n_out letters in all.  The summary has
+ * MC_CONS_COLS int64 per segment: positions, called, ambiguous, nocall, low,
+ * deleted, differs, length; differs counts the positions with r known that
+ * are DEL, or CALLED with a letter other than the reference's;
+ * length = positions - deleted.
+ *
+ * Errors: before begin, and _first / _summary / _get / _device without a
+ * current consensus, MC_E_STATE; negative thresholds, call_ppm > 10^6, unknown
+ * flag bits, MC_CONS_FILL_REF with ref == NULL, and a _get range outside the
+ * aligned buffer [0, N] (compact == 0) or the compact one [0, n_out],
+ * MC_E_INVALID.  Results stay in device memory owned by the handle (buffers
+ * only grow; mc_bases_consensus_device exposes both letter buffers) until the
+ * next mc_bases_consensus, _add_batch, _set or _begin; they share nothing with
+ * the sites buffers, so sites survive a consensus call and the other way
+ * round.  mc_bases_consensus_timing: HIP-event times of the last call's three
+ * launches.  Device side: a call kernel (one workgroup per tile: planes and
+ * ref read once, the letter stored, eight counts per tile by wave reductions
+ * and one LDS step), a one-workgroup scan (prefix sums of the eight columns
+ * over the tiles; out_first and the summary rows are their differences at the
+ * segments' tile ranges) and an emit kernel that compacts the aligned letters
+ * (1 B read per position) by ballot ranks.  No global atomics.
+ *
+ * mc_bases_set (test hook): overwrites plane positions [first, first + count)
+ * from in[6][count] (host memory; any counts up to 2^32 - 1, MC_E_INVALID
+ * outside [0, N]) and invalidates sites and consensus results. */
+#define MC_CONS_IUPAC    1u
+#define MC_CONS_FILL_REF 2u
+#define MC_CONS_COLS     8
+int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t call_ppm, uint32_t flags,
+                       const uint8_t* ref /* N, or NULL */, int64_t* n_out /* compact letters in all */);
+int mc_bases_consensus_first(const mc_bases* h, int64_t* out_first /* S + 1 */);
+int mc_bases_consensus_summary(const mc_bases* h, int64_t* rows /* S x 8 */);
+int mc_bases_consensus_get(const mc_bases* h, int compact, int64_t first, int64_t count, uint8_t* letters);
+int mc_bases_consensus_device(const mc_bases* h, const uint8_t** d_aligned, const uint8_t** d_compact);
+int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, float* scan_ms, float* emit_ms);
+int mc_bases_set(mc_bases* h, int64_t first, int64_t count, const uint32_t* in /* 6 x count */);
 
 typedef struct mc_bases_src mc_bases_src;
 int mc_bases_src_open(const char* path, int n_threads, uint32_t flag_filter, int min_mapq, mc_bases_src** out);

@@ -152,6 +152,14 @@ SIGNATURES = {
     "mc_bases_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                         ctypes.POINTER(ctypes.c_float), _PI64, _PI64],
     "mc_bases_dims": [_PI32],
+    "mc_bases_consensus": [_P, _I64, _I64, _I64, _U32, _P, _PI64],
+    "mc_bases_consensus_first": [_P, _P],
+    "mc_bases_consensus_summary": [_P, _P],
+    "mc_bases_consensus_get": [_P, ctypes.c_int, _I64, _I64, _P],
+    "mc_bases_consensus_device": [_P, _PP, _PP],
+    "mc_bases_consensus_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                  ctypes.POINTER(ctypes.c_float)],
+    "mc_bases_set": [_P, _I64, _I64, _P],
     "mc_bases_src_open": [ctypes.c_char_p, ctypes.c_int, _U32, ctypes.c_int, _PP],
     "mc_bases_src_close": [_P],
     "mc_bases_src_n_targets": [_P, _PI32],

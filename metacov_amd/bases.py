@@ -5,8 +5,11 @@
         bc.add_bam("x.bam")                  # or add_reads(...) batch by batch
         planes = bc.counts()                 # uint32 [6, N]: A, C, G, T, N, DEL
         sites = bc.sites(min_depth=10, min_count=2, min_ppm=10000)
+        cons = bc.consensus(min_depth=10, min_count=2, call_ppm=500000)
+        write_fasta(fh, "contig_1", cons.compact(0))   # the letters were called on the device
 
     a, c, g, t = count_coverage("x.bam", "contig_1", 0, 1000)
+    letters, summary = consensus("x.bam", "contig_1")
 
 The pileup runs on the GPU (csrc/bases.hip, mc_bases_* in
 include/metacov_amd.h); the records come from the host source in
@@ -16,7 +19,8 @@ bounds the path end to end) or from the GPU decoder's bases mode
 decode and pileup).  These are the numbers of pysam's `AlignmentFile.count_coverage()`,
 `samtools mpileup`, pysamstats and bam-readcount; the reference has no
 counterpart.  The contract (CIGAR walk, channels, quality rule, segments,
-sites) is the header's.
+sites, the consensus rule) is the header's.  A consensus never contains
+inserted bases: the planes hold none.
 """
 import ctypes
 
@@ -51,6 +55,40 @@ class Sites:
 
     def __len__(self):
         return len(self.pos)
+
+
+CONS_IUPAC, CONS_FILL_REF = 1, 2    # MC_CONS_*
+CONS_COLS = 8
+# the summary's columns
+POSITIONS, CALLED, AMBIGUOUS, NOCALL, LOW, DELETED, DIFFERS, LENGTH = range(8)
+SUMMARY_COLUMNS = ("positions", "called", "ambiguous", "nocall", "low", "deleted", "differs", "length")
+
+
+class Consensus:
+    """The consensus of S segments (BaseCounter.consensus), valid until the
+    counter's next consensus, add_*, set_counts or begin.  first [S + 1]:
+    segment s owns compact letters first[s] .. first[s + 1]; summary [S, 8]
+    int64 (columns POSITIONS .. LENGTH); n: compact letters in all.  The
+    letters stay on the device; aligned(s) and compact(s) fetch one segment's
+    as uint8 ASCII, GET_CHUNK at a time.  No inserted bases, ever."""
+
+    def __init__(self, counter, seg_off, first, summary, n):
+        self._bc = counter
+        self.seg_off = np.asarray(seg_off, np.int64)
+        self.first = np.asarray(first, np.int64)
+        self.summary = np.asarray(summary, np.int64).reshape(-1, CONS_COLS)
+        self.n = int(n)
+
+    def __len__(self):
+        return len(self.first) - 1
+
+    def aligned(self, s):
+        """One letter per position of segment s, '-' where it is deleted."""
+        return self._bc.consensus_letters(False, int(self.seg_off[s]), int(self.seg_off[s + 1] - self.seg_off[s]))
+
+    def compact(self, s):
+        """Segment s's letters without the deleted positions."""
+        return self._bc.consensus_letters(True, int(self.first[s]), int(self.first[s + 1] - self.first[s]))
 
 
 class BaseSource:
@@ -332,6 +370,54 @@ class BaseCounter:
         check(self._lib.mc_bases_sites_get(self._h, 0, n, ptr(pos), ptr(cnt)), self._lib)
         return Sites(first, pos, cnt)
 
+    def set_counts(self, first, planes):
+        """Test hook (mc_bases_set): overwrites plane indices first .. first +
+        count with planes, uint32 [6, count]; sites and consensus results are
+        gone afterwards."""
+        planes = np.ascontiguousarray(planes, dtype=np.uint32)
+        if planes.ndim != 2 or planes.shape[0] != 6:
+            raise ValueError("planes must be [6, count]")
+        check(self._lib.mc_bases_set(self._h, int(first), planes.shape[1], ptr(planes)), self._lib)
+
+    def consensus(self, min_depth=1, min_count=1, call_ppm=0, iupac=False, fill_ref=False, ref=None):
+        """One letter per position, called on the device (see the header,
+        "Consensus"); ref: optional uint8 [N] codes as sites takes them.
+        Returns a Consensus; its letters stay on the device until fetched."""
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, dtype=np.uint8)
+            if len(ref) != int(self.seg_off[-1]):
+                raise ValueError("the reference plane must have one entry per position")
+        flags = (CONS_IUPAC if iupac else 0) | (CONS_FILL_REF if fill_ref else 0)
+        n = ctypes.c_int64()
+        # (an empty plane still counts as given: FILL_REF with N == 0 is valid)
+        p = None if ref is None else ctypes.c_void_p(ref.ctypes.data)
+        check(self._lib.mc_bases_consensus(self._h, int(min_depth), int(min_count), int(call_ppm), flags, p,
+                                           ctypes.byref(n)), self._lib)
+        first = np.zeros(self._S + 1, np.int64)
+        check(self._lib.mc_bases_consensus_first(self._h, ptr(first)), self._lib)
+        summary = np.zeros((self._S, CONS_COLS), np.int64)
+        check(self._lib.mc_bases_consensus_summary(self._h, ptr(summary)), self._lib)
+        return Consensus(self, self.seg_off, first, summary, n.value)
+
+    def consensus_letters(self, compact, first, count):
+        """uint8 [count] of the aligned (compact false) or compact letters,
+        copied GET_CHUNK at a time."""
+        out = np.zeros(max(int(count), 0), np.uint8)
+        if count <= 0:
+            check(self._lib.mc_bases_consensus_get(self._h, int(bool(compact)), int(first), int(count), None),
+                  self._lib)
+        for a in range(0, int(count), GET_CHUNK):
+            n = min(GET_CHUNK, int(count) - a)
+            check(self._lib.mc_bases_consensus_get(self._h, int(bool(compact)), int(first) + a, n,
+                                                   ctypes.c_void_p(out.ctypes.data + a)), self._lib)
+        return out
+
+    def consensus_timing(self):
+        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        check(self._lib.mc_bases_consensus_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+              self._lib)
+        return {"call_ms": a.value, "scan_ms": b.value, "emit_ms": c.value}
+
     def timing(self):
         a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         t, r = ctypes.c_int64(), ctypes.c_int64()
@@ -400,3 +486,78 @@ def write_sites(fh, name, pos, counts, ref=None):
     fh.write("\n".join(line.tolist()))
     fh.write("\n")
     return n
+
+
+# --------------------------------------------------------------- consensus
+
+SUMMARY_HEADER = "contig\tstart\tend\t" + "\t".join(SUMMARY_COLUMNS) + "\n"
+
+
+def write_fasta(fh, name, letters, width=60):
+    """One FASTA record: `>name`, then the uint8 ASCII letters in lines of
+    `width` (0: one line), wrapped in numpy.  An empty sequence writes the
+    header alone."""
+    letters = np.asarray(letters, np.uint8).reshape(-1)
+    n = len(letters)
+    fh.write(">%s\n" % name)
+    if n == 0:
+        return
+    if width <= 0 or n <= width:
+        fh.write(letters.tobytes().decode("ascii"))
+        fh.write("\n")
+        return
+    full, rest = divmod(n, int(width))
+    out = np.empty(n + full + (1 if rest else 0), np.uint8)
+    body = out[:full * (width + 1)].reshape(full, width + 1)
+    body[:, :width] = letters[:full * width].reshape(full, width)
+    body[:, width] = 10
+    if rest:
+        out[full * (width + 1):-1] = letters[full * width:]
+        out[-1] = 10
+    fh.write(out.tobytes().decode("ascii"))
+
+
+def write_consensus_summary(fh, names, starts, ends, summary, header=True):
+    """Tab-separated `contig start end positions called ambiguous nocall low
+    deleted differs length`, one line per segment (start, end 0-based,
+    half-open); returns the lines written."""
+    if header:
+        fh.write(SUMMARY_HEADER)
+    summary = np.asarray(summary, np.int64).reshape(-1, CONS_COLS)
+    for name, a, b, row in zip(names, starts, ends, summary.tolist()):
+        fh.write("%s\t%d\t%d\t%s\n" % (name, int(a), int(b), "\t".join(str(v) for v in row)))
+    return len(summary)
+
+
+def consensus(path, contig, start=None, stop=None, quality_threshold=0, min_mapq=0, min_depth=1, min_count=1,
+              call_ppm=0, iupac=False, fill_ref=False, ref=None, aligned=False, device=0, decode="host"):
+    """The consensus of [start, stop) of one contig (default: all of it) in
+    one call: (letters uint8, summary int64 [8]).  aligned: keep '-' for the
+    deleted positions, one letter per reference position.  ref: optional
+    ASCII letters (str, bytes or uint8) of the same range.  decode: as
+    add_bam."""
+    if decode not in ("host", "gpu"):
+        raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
+    lib = _lib.load()
+    with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
+        names = [w.split()[0] if w.split() else w for w in src.references]
+        if contig not in names:
+            raise KeyError("contig '%s' is not in the header of %s" % (contig, path))
+        tid = names.index(contig)
+        length = src.lengths[tid]
+    start = 0 if start is None else int(start)
+    stop = length if stop is None else int(stop)
+    if start < 0 or stop < start:
+        raise ValueError("bad range [%d, %d)" % (start, stop))
+    codes = None
+    if ref is not None:
+        if isinstance(ref, str):
+            ref = ref.encode("ascii")
+        codes = ref_codes(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref)
+        if len(codes) != stop - start:
+            raise ValueError("ref must have stop - start letters")
+    with BaseCounter(len(names), device, lib) as bc:
+        bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
+        bc.add_bam(path, min_mapq=min_mapq, decode=decode)
+        c = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes)
+        return (c.aligned(0) if aligned else c.compact(0)), c.summary[0].copy()

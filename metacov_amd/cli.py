@@ -43,6 +43,17 @@ writes `contig pos ref depth A C G T N DEL` for the variant sites, or with
 process, no read cap, `pos` 1-based.  `--decode gpu` also decodes the BAM on
 the GPU, once, and keeps the records in device memory.
 
+Consensus (no counterpart in the reference either):
+
+    python -m metacov_amd.cli consensus -b X.bam [-o out.fa] [-f ref.fa] [-rc R.csv | -rb R.blast7] [--min-baseq 0]
+                                        [--min-mapq 0] [--min-depth 1] [--min-count 1] [--call-frac 0.0] [--iupac]
+                                        [--fill-ref] [--aligned] [--summary FILE] [--line-width 60]
+                                        [--decode host|gpu]
+
+writes one FASTA record per contig or region, called per position from the
+same counts on the GPU: the strongest of A, C, G, T and deletion if it passes
+the thresholds, else N.  It never contains inserted bases.
+
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
     python -m torch.distributed.run --nproc-per-node 8 -m metacov_amd.cli pileup -b X.bam ...
@@ -870,6 +881,144 @@ def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, 
         log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
                  "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
     log.info("%d lines written", n)
+    if err is not None:      # the regions before a failing one are written first, as pileup does
+        raise err
+
+
+def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta=None, device=0, min_baseq=0,
+                    min_mapq=0, min_depth=1, min_count=1, call_ppm=0, iupac=False, fill_ref=False, aligned=False,
+                    summary=None, line_width=60, decode="host"):
+    """One FASTA record per segment (header contig ids, record names
+    `labels`), group by group as write_bases does it, each written before the
+    next is computed; `summary`: also the per-segment table.  Returns
+    (records written, the source's record counts)."""
+    from . import bases as _bases
+    import contextlib
+    names = [w.split()[0] if w.split() else w for w in references]
+    if summary is not None:
+        summary.write(_bases.SUMMARY_HEADER)
+    counts = None
+    if len(tids) == 0:
+        return 0, None
+    fa = _experimental.FastaFile(fasta) if fasta else None
+    with contextlib.ExitStack() as stack:
+        bc = stack.enter_context(_bases.BaseCounter(len(references), device))
+        src = None
+        if decode == "gpu":
+            try:
+                src = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
+            except _bases._lib.MetacovError as e:
+                if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
+                    raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
+                                               "run with --decode host (%s)" % (path, device, e))
+                raise
+        for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
+            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
+            if src is not None:
+                bc.add_device(src)
+                counts = src.counts()
+            else:
+                counts = bc.add_bam(path, min_mapq=min_mapq)
+            codes = None
+            if fa is not None:
+                codes = _bases.ref_codes(np.concatenate(
+                    [_segment_letters(fa, names[int(tids[i])], starts[i], ends[i]) for i in range(a, b)] +
+                    [np.zeros(0, np.uint8)]))
+            cons = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes)
+            for i in range(a, b):
+                _bases.write_fasta(outfile, labels[i], cons.aligned(i - a) if aligned else cons.compact(i - a),
+                                   line_width)
+            if summary is not None:
+                _bases.write_consensus_summary(summary, [names[int(t)] for t in tids[a:b]], starts[a:b], ends[a:b],
+                                               cons.summary, header=False)
+    return len(tids), counts
+
+
+@main.command()
+@click.option('--bamfile', '-b', type=click.File('rb'), required=True,
+              help="Input BAM file. Must be coordinate-sorted.")
+@click.option('--outfile', '-o', type=click.File('w'), default="-",
+              help="Output FASTA (default STDOUT)")
+@click.option('--reference-fasta', '-f', type=click.File('rb'),
+              help="Reference FASTA (plain or gzip): counts the differences for --summary and serves --fill-ref")
+@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
+              help="Input Region file in BLAST7 format")
+@click.option('--regionfile-csv', '-rc', type=click.File('r'),
+              help="Input Region file in CSV format")
+@click.option('--min-baseq', type=click.IntRange(0), default=0,
+              help="Count only bases of at least this quality (deletions always count)")
+@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
+              help="Use only reads of at least this mapping quality")
+@click.option('--min-depth', type=click.IntRange(0), default=1, show_default=True,
+              help="Below this A + C + G + T + DEL a position is N (or the reference base with --fill-ref)")
+@click.option('--min-count', type=click.IntRange(0), default=1, show_default=True,
+              help="A called allele needs this many reads")
+@click.option('--call-frac', type=float, default=0.0, show_default=True,
+              help="A called allele needs this fraction (0..1) of the depth")
+@click.option('--iupac', is_flag=True, default=False,
+              help="Where two to four bases pass --min-count and --call-frac, write their IUPAC code")
+@click.option('--fill-ref', is_flag=True, default=False,
+              help="Write the reference base in lower case where the depth is below --min-depth (needs -f)")
+@click.option('--aligned', is_flag=True, default=False,
+              help="Keep deleted positions as `-`: one letter per reference position, reference coordinates")
+@click.option('--summary', type=click.File('w'), metavar="FILE",
+              help="Also write `contig start end positions called ambiguous nocall low deleted differs length` "
+                   "per record")
+@click.option('--line-width', type=click.IntRange(0), default=60, show_default=True,
+              help="Letters per FASTA line; 0: no wrap")
+@click.option('--device', type=int, default=0, help="HIP device ordinal")
+@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
+              help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
+                   "the GPU, the records staying in device memory (the file's reads must fit there)")
+def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, min_baseq, min_mapq, min_depth,
+              min_count, call_frac, iupac, fill_ref, aligned, summary, line_width, device, decode):
+    """
+    Write the consensus sequence of the reads as FASTA
+
+    One record per contig in header order (named by the contig id), or per
+    region of a region file in file order (named `name:START-END`, 1-based
+    inclusive).  Per position the allele with the highest count among A, C, G,
+    T and deletion is called if it passes --min-count and --call-frac; a
+    called deletion is left out (or `-` with --aligned), anything else is N.
+    The consensus never contains inserted bases: insertions in the reads are
+    not counted.  Called on the GPU; single process only.
+    """
+    from . import bases as _bases
+    if regionfile_blast7 and regionfile_csv:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    if not 0.0 <= call_frac <= 1.0:         # (nan fails both comparisons)
+        raise click.BadParameter("must lie in [0, 1]", param_hint="--call-frac")
+    if fill_ref and not reference_fasta:
+        raise click.BadParameter("needs a reference (-f)", param_hint="--fill-ref")
+    call_ppm = int(round(call_frac * 1e6))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("consensus runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)")
+    fasta = reference_fasta.name if reference_fasta else None
+    with _bases.BaseSource(bamfile.name) as head:
+        references, lengths = list(head.references), list(head.lengths)
+    names = [w.split()[0] if w.split() else w for w in references]
+    err = None
+    if regionfile_blast7 or regionfile_csv:
+        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
+        _, tids, starts, ends, err = resolve_regions(head, regions)
+        labels = ["%s:%d-%d" % (names[int(t)], a + 1, b) for t, a, b in zip(tids, starts, ends)]
+    else:
+        tids = np.arange(len(lengths), dtype=np.int32)
+        starts = np.zeros(len(tids), np.int64)
+        ends = np.asarray(lengths, np.int64)
+        labels = names
+    n, counts = write_consensus(bamfile.name, references, tids, starts, ends, labels, outfile, fasta=fasta,
+                                device=device, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
+                                min_count=min_count, call_ppm=call_ppm, iupac=iupac, fill_ref=fill_ref,
+                                aligned=aligned, summary=summary, line_width=line_width, decode=decode)
+    outfile.flush()
+    if summary is not None:
+        summary.flush()
+    if counts:
+        log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
+                 "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    log.info("%d sequences written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err
 

@@ -45,6 +45,8 @@
 //   sites_count / scan / emit   the count - scan - emit pattern of runs.hip
 //                         over the planes with the site predicate; the host
 //                         reads the total (8 bytes) between scan and emit.
+//   cons_call / scan / emit     the consensus letters (see the kernels): the
+//                         same pattern, the emit over the 1-byte letters.
 //
 // A tile whose first plane index is not 16-byte aligned starts `lead` (1..3)
 // elements into its LDS window and holds at most kTile - lead positions, so
@@ -391,6 +393,204 @@ __global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __
     }
 }
 
+// ---- consensus (the rule is the header's, "Consensus") ----------------------
+// cons_call_kernel   one workgroup per tile, the sites kernels' position-to-
+//                    thread mapping: five planes and the optional ref read
+//                    once, one letter per position into the aligned buffer
+//                    (a wave stores 64 consecutive bytes), the tile's eight
+//                    summary columns through wave reductions and one LDS step.
+// cons_scan_kernel   one workgroup: exclusive prefix sums over the tiles of
+//                    each of the eight columns; out_first and the summary rows
+//                    are differences of them at the segments' tile ranges.
+// cons_emit_kernel   one workgroup per tile: reads the aligned letters (1 B per
+//                    position) and writes those that are not '-' in position
+//                    order, by ballot ranks per round and wave.
+// No global atomics; every loop is bounded by the tile size or the tile count.
+
+constexpr int kConsCols = MC_CONS_COLS;             // positions called ambiguous nocall low deleted differs length
+
+struct ConsArgs {
+    unsigned long long min_depth, min_count, call_ppm;   // min_depth and min_count already raised to 1
+    uint32_t flags;
+};
+
+__device__ __forceinline__ bool cons_qualifies(uint32_t x, unsigned long long depth, const ConsArgs& c) {
+    return x >= c.min_count && (unsigned long long)x * 1000000ull >= c.call_ppm * depth;
+}
+
+// The letter of a position with counts a[0..4] (A C G T DEL) and reference
+// code r.  Its class is counted into packed 10-bit counters: w0 holds called,
+// ambiguous, no call at bits 0, 10, 20; w1 holds low, deleted, differs.
+__device__ __forceinline__ uint32_t cons_letter(const uint32_t (&a)[5], uint32_t r, const ConsArgs& c,
+                                                uint32_t& w0, uint32_t& w1) {
+    const unsigned long long depth = (unsigned long long)a[0] + a[1] + a[2] + a[3] + a[4];
+    const bool known = r < 4;
+    if (depth < c.min_depth) {
+        w1 += 1u;
+        return ((c.flags & MC_CONS_FILL_REF) && known) ? ((0x74676361u >> (8 * r)) & 0xFFu) : (uint32_t)'N';
+    }
+    int top = 0;
+#pragma unroll
+    for (int i = 1; i < 5; ++i)
+        if (a[i] > a[top]) top = i;
+    if (top == 4) {
+        if (!cons_qualifies(a[4], depth, c)) {
+            w0 += 1u << 20;
+            return 'N';
+        }
+        w1 += (1u << 10) + (known ? 1u << 20 : 0u);
+        return '-';
+    }
+    uint32_t mask = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mask |= (uint32_t)cons_qualifies(a[i], depth, c) << i;
+    if (!(c.flags & MC_CONS_IUPAC)) mask &= 1u << top;
+    if (mask == 0) {
+        w0 += 1u << 20;
+        return 'N';
+    }
+    // ".ACMGRSV" and "TWYHKDBN", eight letters per 64-bit word, the first in the low byte
+    const unsigned long long tab = mask < 8 ? 0x565352474D43412Eull : 0x4E42444B48595754ull;
+    const uint32_t letter = (uint32_t)(tab >> (8 * (mask & 7u))) & 0xFFu;
+    if (mask & (mask - 1)) {
+        w0 += 1u << 10;
+    } else {
+        w0 += 1u;
+        if (known && (uint32_t)top != r) w1 += 1u << 20;
+    }
+    return letter;
+}
+
+__global__ __launch_bounds__(kThreads) void cons_call_kernel(const uint32_t* __restrict__ planes, int64_t stride,
+                                                            const uint8_t* __restrict__ ref,
+                                                            const Tile* __restrict__ tiles, int64_t n_tiles,
+                                                            ConsArgs ca, uint8_t* __restrict__ aligned,
+                                                            int32_t* __restrict__ cols) {
+    __shared__ uint32_t wsum[kWaves][2];
+    const Tile t = tiles[blockIdx.x];
+    uint32_t w0 = 0, w1 = 0;            // three 10-bit counters each: at most 4 per thread, 256 per wave
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const int k = r * kThreads + (int)threadIdx.x;
+        if (k < t.n) {
+            const int64_t i = t.out + k;
+            const uint32_t a[5] = {planes[i], planes[stride + i], planes[2 * stride + i], planes[3 * stride + i],
+                                   planes[5 * stride + i]};
+            aligned[i] = (uint8_t)cons_letter(a, ref ? (uint32_t)ref[i] : 4u, ca, w0, w1);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        w0 += __shfl_xor(w0, off, 64);
+        w1 += __shfl_xor(w1, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wsum[threadIdx.x >> 6][0] = w0;
+        wsum[threadIdx.x >> 6][1] = w1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {              // thread c sums counter c of the eight waves
+        const int word = threadIdx.x / 3, shift = 10 * (threadIdx.x % 3);
+        int32_t sum = 0;
+        for (int w = 0; w < kWaves; ++w) sum += (int32_t)((wsum[w][word] >> shift) & 0x3FFu);
+        cols[(1 + (int64_t)threadIdx.x) * n_tiles + blockIdx.x] = sum;
+        if (threadIdx.x == 4) {         // deleted: the kept count beside it
+            cols[blockIdx.x] = t.n;
+            cols[7 * n_tiles + blockIdx.x] = t.n - sum;
+        }
+    }
+}
+
+// One workgroup.  For each column c: pre[c][i] = sum of cols[c][0, i) for
+// i <= n_tiles (sites_scan_kernel's scan; a tile's entry is at most kTile, an
+// iteration's sum below 2^24).  Then out_first[s] = pre[7][seg_tile[s]] and
+// rows[s][c] = pre[c][seg_tile[s + 1]] - pre[c][seg_tile[s]]: a segment's
+// tiles are contiguous, an empty segment has none.
+__global__ __launch_bounds__(kScanThreads) void cons_scan_kernel(const int32_t* __restrict__ cols, int64_t n_tiles,
+                                                                int64_t* __restrict__ pre,
+                                                                const int64_t* __restrict__ seg_tile, int64_t S,
+                                                                int64_t* __restrict__ out_first,
+                                                                int64_t* __restrict__ rows) {
+    __shared__ int32_t wsum[kScanThreads / 64];
+    __shared__ int64_t carry_s;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    for (int col = 0; col < kConsCols; ++col) {
+        const int32_t* __restrict__ src = cols + col * n_tiles;
+        int64_t* __restrict__ dst = pre + col * (n_tiles + 1);
+        if (t == 0) carry_s = 0;
+        __syncthreads();
+        for (int64_t i0 = 0; i0 < n_tiles; i0 += kScanWidth) {
+            const int64_t i = i0 + 4 * (int64_t)t;
+            int32_t c[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[k] = i + k < n_tiles ? src[i + k] : 0;
+            const int32_t mine = c[0] + c[1] + c[2] + c[3];
+            int32_t inc = mine;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int32_t o = __shfl_up(inc, off, 64);
+                if (lane >= off) inc += o;
+            }
+            if (lane == 63) wsum[wave] = inc;
+            __syncthreads();
+            int32_t wbase = 0, total = 0;
+            for (int w = 0; w < kScanThreads / 64; ++w) {
+                if (w < wave) wbase += wsum[w];
+                total += wsum[w];
+            }
+            int64_t bs = carry_s + wbase + (inc - mine);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (i + k < n_tiles) dst[i + k] = bs;
+                bs += c[k];
+            }
+            __syncthreads();                                // every thread has read carry_s and wsum
+            if (t == 0) carry_s += total;
+            __syncthreads();
+        }
+        if (t == 0) dst[n_tiles] = carry_s;
+        __syncthreads();                                    // carry_s is free for the next column
+    }
+    // (pre[] is visible to this workgroup after the barrier above)
+    for (int64_t s = t; s <= S; s += kScanThreads) out_first[s] = pre[7 * (n_tiles + 1) + seg_tile[s]];
+    for (int64_t j = t; j < S * kConsCols; j += kScanThreads) {
+        const int64_t s = j / kConsCols, col = j % kConsCols;
+        const int64_t* p = pre + col * (n_tiles + 1);
+        rows[j] = p[seg_tile[s + 1]] - p[seg_tile[s]];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void cons_emit_kernel(const uint8_t* __restrict__ aligned,
+                                                            const Tile* __restrict__ tiles,
+                                                            const int64_t* __restrict__ base,
+                                                            uint8_t* __restrict__ compact) {
+    __shared__ int32_t wcnt[kRounds][kWaves];
+    const Tile t = tiles[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t letter[kRounds];
+    int32_t rank[kRounds];                                  // kept letters of this round in lower lanes of the wave
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const int k = r * kThreads + (int)threadIdx.x;
+        letter[r] = k < t.n ? (uint32_t)aligned[t.out + k] : (uint32_t)'-';
+        const unsigned long long m = __ballot(letter[r] != (uint32_t)'-');
+        rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        if (lane == 0) wcnt[r][wave] = __popcll(m);
+    }
+    __syncthreads();
+    int64_t run = base[blockIdx.x];                         // positions ascend with (round, wave, lane)
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        int64_t mine = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            if (w == wave) mine = run;
+            run += wcnt[r][w];
+        }
+        if (letter[r] != (uint32_t)'-') compact[mine + rank[r]] = (uint8_t)letter[r];
+    }
+}
+
 }  // namespace
 
 #define HIP_TRY(expr)                                                          \
@@ -462,8 +662,18 @@ struct mc_bases {
     Buf<int64_t> base, site_first, site_pos;
     Buf<uint32_t> site_counts;
     float ms_prepass = 0, ms_pileup = 0, ms_sites = 0;
+    // consensus: buffers of its own, so sites and a consensus live side by side
+    bool have_cons = false;
+    int64_t n_cons = 0;                  // compact letters in all
+    hipEvent_t cev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    Buf<uint8_t> cons_ref, cons_aligned, cons_compact;
+    Buf<int32_t> cons_cols;              // [8][T]
+    Buf<int64_t> cons_pre, cons_first, cons_rows;   // [8][T + 1], [S + 1], [S][8]
+    float ms_cons_call = 0, ms_cons_scan = 0, ms_cons_emit = 0;
     ~mc_bases() {
         for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto& e : cev)
             if (e) (void)hipEventDestroy(e);
         if (pin) (void)hipHostFree(pin);
         if (stream) (void)hipStreamDestroy(stream);
@@ -485,6 +695,7 @@ extern "C" int mc_bases_create(int device, int32_t n_ref, mc_bases** out) {
               hipHostMalloc((void**)&h->pin, 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
               h->flags.reserve(2) == hipSuccess;
     for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (auto& e : h->cev) ok = ok && hipEventCreate(&e) == hipSuccess;
     if (!ok) {
         delete h;
         mc::set_error("HIP stream / event creation failed");
@@ -515,6 +726,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     MC_REQUIRE(min_baseq >= 0, MC_E_INVALID, "min_baseq %d is negative", min_baseq);
     h->begun = false;
     h->have_sites = false;
+    h->have_cons = false;
 
     // ---- tile table (host): a tile never spans two segments
     std::vector<Tile> tiles;
@@ -578,6 +790,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->have_last = false;
     h->n_reads = 0;
     h->ms_prepass = h->ms_pileup = h->ms_sites = 0;
+    h->ms_cons_call = h->ms_cons_scan = h->ms_cons_emit = 0;
     h->begun = true;
     return MC_OK;
 }
@@ -705,6 +918,7 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     h->last_pos = pos[n - 1];
     h->n_reads += n;
     h->have_sites = false;
+    h->have_cons = false;
     return MC_OK;
 }
 
@@ -823,6 +1037,7 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
     h->last_pos = ends[3];
     h->n_reads += n;
     h->have_sites = false;
+    h->have_cons = false;
     return MC_OK;
 }
 
@@ -944,5 +1159,138 @@ extern "C" int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pile
     *sites_ms = h->ms_sites;
     *tiles = h->n_tiles;
     *reads = h->n_reads;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_set(mc_bases* h, int64_t first, int64_t count, const uint32_t* in) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
+               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
+               (long long)count, (long long)h->N);
+    MC_REQUIRE(count == 0 || in, MC_E_INVALID, "null in");
+    h->have_sites = false;
+    h->have_cons = false;
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    for (int c = 0; c < kPlanes; ++c)
+        HIP_TRY(hipMemcpyAsync(h->planes.p + c * h->stride + first, in + (size_t)c * (size_t)count, (size_t)count * 4,
+                               hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t call_ppm,
+                                  uint32_t flags, const uint8_t* ref, int64_t* n_out) {
+    MC_REQUIRE(h && n_out, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(min_depth >= 0 && min_count >= 0 && call_ppm >= 0 && call_ppm <= 1000000, MC_E_INVALID,
+               "consensus thresholds out of range (min_depth %lld, min_count %lld, call_ppm %lld of 10^6)",
+               (long long)min_depth, (long long)min_count, (long long)call_ppm);
+    MC_REQUIRE((flags & ~(MC_CONS_IUPAC | MC_CONS_FILL_REF)) == 0, MC_E_INVALID, "unknown consensus flags 0x%x",
+               flags);
+    MC_REQUIRE(!(flags & MC_CONS_FILL_REF) || ref, MC_E_INVALID, "MC_CONS_FILL_REF needs a reference plane");
+    h->have_cons = false;
+    const int64_t T = h->n_tiles, S = h->S;
+    const ConsArgs ca{(unsigned long long)std::max<int64_t>(min_depth, 1),
+                      (unsigned long long)std::max<int64_t>(min_count, 1), (unsigned long long)call_ppm, flags};
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->cons_aligned.reserve((size_t)h->N));
+    HIP_TRY(h->cons_cols.reserve((size_t)(kConsCols * T)));
+    HIP_TRY(h->cons_pre.reserve((size_t)(kConsCols * (T + 1))));
+    HIP_TRY(h->cons_first.reserve((size_t)S + 1));
+    HIP_TRY(h->cons_rows.reserve((size_t)(S * kConsCols)));
+    hipStream_t st = h->stream;
+    const uint8_t* d_ref = nullptr;
+    if (ref && h->N) {
+        HIP_TRY(h->cons_ref.reserve((size_t)h->N));
+        HIP_TRY(hipMemcpyAsync(h->cons_ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, st));
+        d_ref = h->cons_ref.p;
+    }
+    HIP_TRY(hipEventRecord(h->cev[0], st));
+    if (T) {
+        hipLaunchKernelGGL(cons_call_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
+                           h->tiles.p, T, ca, h->cons_aligned.p, h->cons_cols.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->cev[1], st));
+    hipLaunchKernelGGL(cons_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->cons_cols.p, T, h->cons_pre.p,
+                       h->seg_tile.p, S, h->cons_first.p, h->cons_rows.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->cev[2], st));
+    HIP_TRY(hipMemcpyAsync(h->pin + 3, h->cons_pre.p + 7 * (T + 1) + T, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int64_t total = 0;
+    std::memcpy(&total, h->pin + 3, 8);
+    MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "consensus length %lld out of range", (long long)total);
+    HIP_TRY(h->cons_compact.reserve((size_t)total));
+    HIP_TRY(hipEventRecord(h->cev[3], st));
+    if (T) {
+        hipLaunchKernelGGL(cons_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->cons_aligned.p, h->tiles.p,
+                           h->cons_pre.p + 7 * (T + 1), h->cons_compact.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->cev[4], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&h->ms_cons_call, h->cev[0], h->cev[1]));
+    HIP_TRY(hipEventElapsedTime(&h->ms_cons_scan, h->cev[1], h->cev[2]));
+    HIP_TRY(hipEventElapsedTime(&h->ms_cons_emit, h->cev[3], h->cev[4]));
+    h->n_cons = total;
+    h->have_cons = true;
+    *n_out = total;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus_first(const mc_bases* h, int64_t* out_first) {
+    MC_REQUIRE(h && out_first, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_cons, MC_E_STATE, "no consensus computed (call mc_bases_consensus)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(out_first, h->cons_first.p, ((size_t)h->S + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus_summary(const mc_bases* h, int64_t* rows) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_cons, MC_E_STATE, "no consensus computed (call mc_bases_consensus)");
+    MC_REQUIRE(h->S == 0 || rows, MC_E_INVALID, "null rows");
+    if (h->S == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(rows, h->cons_rows.p, (size_t)h->S * kConsCols * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus_get(const mc_bases* h, int compact, int64_t first, int64_t count,
+                                      uint8_t* letters) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_cons, MC_E_STATE, "no consensus computed (call mc_bases_consensus)");
+    const int64_t n = compact ? h->n_cons : h->N;
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= n && count <= n - first, MC_E_INVALID,
+               "%s letters [%lld, %lld + %lld) outside [0, %lld]", compact ? "compact" : "aligned", (long long)first,
+               (long long)first, (long long)count, (long long)n);
+    MC_REQUIRE(count == 0 || letters, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(letters, (compact ? h->cons_compact.p : h->cons_aligned.p) + first, (size_t)count,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus_device(const mc_bases* h, const uint8_t** d_aligned, const uint8_t** d_compact) {
+    MC_REQUIRE(h && d_aligned && d_compact, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_cons, MC_E_STATE, "no consensus computed (call mc_bases_consensus)");
+    *d_aligned = h->cons_aligned.p;
+    *d_compact = h->cons_compact.p;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, float* scan_ms, float* emit_ms) {
+    MC_REQUIRE(h && call_ms && scan_ms && emit_ms, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    *call_ms = h->ms_cons_call;
+    *scan_ms = h->ms_cons_scan;
+    *emit_ms = h->ms_cons_emit;
     return MC_OK;
 }
