@@ -494,9 +494,10 @@ int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pileup_ms, floa
 int mc_bases_dims(int32_t* tile);
 
 /* Consensus (mc_bases_consensus), a third stage over the planes on the device:
- * one letter per position, called from the counts alone.  A consensus built
- * here never contains inserted bases (the planes hold none); insertion
- * alleles are out of scope.  Integer only, exact and deterministic.
+ * one letter per position, called from the counts alone.  Without
+ * MC_CONS_INS a consensus never contains inserted bases (the planes hold
+ * none); with it, see "Insertion alleles" below.  Integer only, exact and
+ * deterministic.
  *
  * At plane index i let a[0..3] be the A, C, G, T counts, d the DEL count (the
  * N plane is ignored, as in sites), depth = a0 + a1 + a2 + a3 + d in 64 bits
@@ -556,6 +557,93 @@ int mc_bases_consensus_get(const mc_bases* h, int compact, int64_t first, int64_
 int mc_bases_consensus_device(const mc_bases* h, const uint8_t** d_aligned, const uint8_t** d_compact);
 int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, float* scan_ms, float* emit_ms);
 int mc_bases_set(mc_bases* h, int64_t first, int64_t count, const uint32_t* in /* 6 x count */);
+
+/* Insertion alleles (csrc/bases_ins.h), an opt-in stage of mc_bases, off by
+ * default: with it off no launch, byte or error of the calls above changes.
+ * The reference has nothing here; the contract is this library's own.
+ *
+ * The walk is the one above: from rpos = pos, qpos = 0.  An I op of length
+ * L >= 1 met at reference cursor rpos > pos (M, =, X, D or N ops of at least
+ * one reference position in all precede it in the read) is an EVENT at anchor
+ * p = rpos - 1, the reference base before the inserted bases (the mpileup and
+ * VCF convention).  A leading insertion (rpos == pos: only S, H, P or I before
+ * it) is ignored, as mpileup ignores it, so every anchor lies in
+ * [pos, pos + span) and the pileup's tile search finds every contributing
+ * read.  A trailing I counts; two I ops of one read at one anchor are two
+ * events; no quality test applies (as for DEL: min_baseq does not touch
+ * insertions).  The event's allele is (len, code): if L <= 32 and all L query
+ * bases qpos .. qpos + L have nt16 codes 1, 2, 4 or 8, len = L and code =
+ * sum of b_j * 4^(L - 1 - j) with A, C, G, T = 0..3 (numeric order of equal
+ * lengths is lexicographic order).  Otherwise (longer, or an ambiguity code
+ * inside) the event is OTHER: len = 0, code = 0, other = 1; OTHER events are
+ * counted and never called.  An event belongs to every plane index i whose
+ * segment holds p (overlapping and duplicated segments each get it, as the
+ * planes do); an anchor outside every segment adds nothing.
+ *
+ * The allele table is the multiset of events, grouped: rows (i int64, len
+ * int32, code uint64, other uint8, count uint32), sorted by (i, other, len,
+ * code) and unique, so a segment's rows are contiguous and a position's OTHER
+ * row is its last.  It is a function of the set of reads alone: the same
+ * reads in any split into batches give identical bytes.  At most 2^31 - 1
+ * events per begin (MC_E_RANGE).
+ *
+ * mc_bases_track_insertions(h, on): on = 1 / 0 makes the NEXT mc_bases_begin
+ * (and those after it) track or not; NULL handle or another value of on is
+ * MC_E_INVALID.  mc_bases_begin clears the events.  On a handle whose current
+ * begin does not track, every call below is MC_E_STATE (before the first begin
+ * too); mc_bases_consensus with MC_CONS_INS is MC_E_INVALID there, the answer
+ * to that flag bit since before it had a meaning.
+ * mc_bases_insertions groups the events and keeps the rows with
+ * depth(i) = A + C + G + T + DEL at i (64 bits), depth >= min_depth, count >=
+ * min_count and count * 10^6 >= min_ppm * depth, the sites predicate:
+ * (0, 1, 0) keeps every row.  Negative thresholds or min_ppm > 10^6:
+ * MC_E_INVALID.  Segment s owns rows [first[s], first[s + 1])
+ * (mc_bases_insertions_first); mc_bases_insertions_get copies rows [first,
+ * first + count) (MC_E_INVALID outside [0, *n_rows] or with a NULL array for
+ * count > 0; both MC_E_STATE without a current table: it is gone after the
+ * next mc_bases_add_batch, _set, _ins_set or _begin).
+ * mc_bases_insertions_timing: HIP-event times of the extract launches since
+ * begin, of the last mc_bases_insertions and of the insertion part of the
+ * last consensus, and the events held.
+ * mc_bases_ins_set (test hook, as mc_bases_set): installs a grouped table of n
+ * rows in place of the events; MC_E_INVALID unless the rows are sorted by
+ * (i, other, len, code) and unique, 0 <= i < N, other is 0 (1 <= len <= 32,
+ * code < 4^len) or 1 (len = 0, code = 0) and count >= 1.  Until the next
+ * begin mc_bases_add_batch and _add_batch_device are then MC_E_STATE.
+ *
+ * MC_CONS_INS for mc_bases_consensus: at each plane index i whose class is not
+ * LOW the TOP allele is the row that is not OTHER with the highest count
+ * (ties: the shorter len, then the smaller code).  If it qualifies
+ * (qualifies(count) of "Consensus", with depth(i)), its len letters, upper
+ * case, follow position i's letter in the COMPACT output; where i was called
+ * DEL they stand where that letter would have been.  One insertion per anchor
+ * at most.  The aligned buffer is unchanged (one letter per position).  With
+ * the flag, out_first, *n_out and the summary's length become positions -
+ * deleted + inserted, and mc_bases_consensus_ins returns per segment the
+ * insertions called and the bases inserted (MC_E_STATE unless the current
+ * consensus was made with the flag).  Without the flag every output is byte
+ * for byte what it was, on tracking handles too.
+ *
+ * Device side: per batch an extract (one workgroup per tile of the pileup
+ * launch's range, one thread per read, CIGAR words only; count pass, scan,
+ * fill pass appending 24-byte events, query bases loaded only inside I ops);
+ * at mc_bases_insertions a scatter into per-tile buckets, one workgroup per
+ * bucket sorting it (bitonic, in LDS up to 4096 events, else over global
+ * memory with LDS for the short strides) and a run-length encode with the
+ * threshold predicate (count pass, scan, emit pass). */
+#define MC_CONS_INS      4u
+int mc_bases_track_insertions(mc_bases* h, int on);
+int mc_bases_insertions(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, int64_t* n_rows);
+int mc_bases_insertions_first(const mc_bases* h, int64_t* first /* S + 1 */);
+int mc_bases_insertions_get(const mc_bases* h, int64_t first, int64_t count, int64_t* i, int32_t* len,
+                            uint64_t* code, uint8_t* other, uint32_t* cnt);
+int mc_bases_insertions_timing(const mc_bases* h, float* extract_ms, float* group_ms, float* cons_ms,
+                               int64_t* events);
+int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const int32_t* len, const uint64_t* code,
+                     const uint8_t* other, const uint32_t* cnt);
+int mc_bases_consensus_ins(const mc_bases* h, int64_t* rows /* S x 2 */);
+/* (test hook) the events one workgroup sorts in LDS, and the longest callable insertion */
+int mc_bases_ins_dims(int32_t* sort_chunk, int32_t* max_len);
 
 typedef struct mc_bases_src mc_bases_src;
 int mc_bases_src_open(const char* path, int n_threads, uint32_t flag_filter, int min_mapq, mc_bases_src** out);

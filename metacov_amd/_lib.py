@@ -160,6 +160,16 @@ SIGNATURES = {
     "mc_bases_consensus_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_float)],
     "mc_bases_set": [_P, _I64, _I64, _P],
+    # insertion alleles (csrc/bases_ins.h)
+    "mc_bases_track_insertions": [_P, ctypes.c_int],
+    "mc_bases_insertions": [_P, _I64, _I64, _I64, _PI64],
+    "mc_bases_insertions_first": [_P, _P],
+    "mc_bases_insertions_get": [_P, _I64, _I64, _P, _P, _P, _P, _P],
+    "mc_bases_insertions_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                   ctypes.POINTER(ctypes.c_float), _PI64],
+    "mc_bases_ins_set": [_P, _I64, _P, _P, _P, _P, _P],
+    "mc_bases_consensus_ins": [_P, _P],
+    "mc_bases_ins_dims": [_PI32, _PI32],
     "mc_bases_src_open": [ctypes.c_char_p, ctypes.c_int, _U32, ctypes.c_int, _PP],
     "mc_bases_src_close": [_P],
     "mc_bases_src_n_targets": [_P, _PI32],

@@ -19,8 +19,10 @@ bounds the path end to end) or from the GPU decoder's bases mode
 decode and pileup).  These are the numbers of pysam's `AlignmentFile.count_coverage()`,
 `samtools mpileup`, pysamstats and bam-readcount; the reference has no
 counterpart.  The contract (CIGAR walk, channels, quality rule, segments,
-sites, the consensus rule) is the header's.  A consensus never contains
-inserted bases: the planes hold none.
+sites, the consensus rule, insertion alleles) is the header's.  Insertions
+are opt-in: begin(..., insertions=True) collects the I ops' alleles beside the
+planes, insertions() returns their grouped table and consensus(...,
+insertions=True) writes the called ones into the compact letters.
 """
 import ctypes
 
@@ -43,6 +45,14 @@ def dims(lib=None):
     return t.value
 
 
+def ins_dims(lib=None):
+    """(events one workgroup sorts in LDS, longest callable insertion)."""
+    lib = lib or _lib.load()
+    a, b = ctypes.c_int32(), ctypes.c_int32()
+    check(lib.mc_bases_ins_dims(ctypes.byref(a), ctypes.byref(b)), lib)
+    return a.value, b.value
+
+
 class Sites:
     """Sites of S segments, in segment order: segment s owns rows
     first[s] .. first[s + 1]; pos [n] int64 relative to the contig, ascending
@@ -57,7 +67,36 @@ class Sites:
         return len(self.pos)
 
 
-CONS_IUPAC, CONS_FILL_REF = 1, 2    # MC_CONS_*
+CONS_IUPAC, CONS_FILL_REF, CONS_INS = 1, 2, 4    # MC_CONS_*
+MAX_INS_LEN = 32                    # a longer insertion is OTHER
+
+
+class Insertions:
+    """The allele table of S segments (BaseCounter.insertions): segment s owns
+    rows first[s] .. first[s + 1], sorted by (index, other, length, code) and
+    unique.  index [n] int64 plane index of the anchor (the position before
+    the inserted bases), length [n] int32 and code [n] uint64 (base j of the
+    allele is (code >> 2 * (length - 1 - j)) & 3, A C G T = 0..3), other [n]
+    uint8 (1: the position's row of insertions longer than MAX_INS_LEN or with
+    an ambiguity code; length 0, code 0), count [n] uint32."""
+
+    def __init__(self, first, index, length, code, other, count):
+        self.first = np.asarray(first, np.int64)
+        self.index = np.asarray(index, np.int64)
+        self.length = np.asarray(length, np.int32)
+        self.code = np.asarray(code, np.uint64)
+        self.other = np.asarray(other, np.uint8)
+        self.count = np.asarray(count, np.uint32)
+
+    def __len__(self):
+        return len(self.index)
+
+    def sequence(self, k):
+        """Row k's inserted bases as a str; '*' for an OTHER row."""
+        if self.other[k]:
+            return "*"
+        n, c = int(self.length[k]), int(self.code[k])
+        return "".join("ACGT"[(c >> (2 * (n - 1 - j))) & 3] for j in range(n))
 CONS_COLS = 8
 # the summary's columns
 POSITIONS, CALLED, AMBIGUOUS, NOCALL, LOW, DELETED, DIFFERS, LENGTH = range(8)
@@ -70,10 +109,13 @@ class Consensus:
     segment s owns compact letters first[s] .. first[s + 1]; summary [S, 8]
     int64 (columns POSITIONS .. LENGTH); n: compact letters in all.  The
     letters stay on the device; aligned(s) and compact(s) fetch one segment's
-    as uint8 ASCII, GET_CHUNK at a time.  No inserted bases, ever."""
+    as uint8 ASCII, GET_CHUNK at a time.  inserted: None, or with
+    insertions=True int64 [S, 2]: insertions called, bases inserted (the
+    compact letters and the summary's length then include them)."""
 
-    def __init__(self, counter, seg_off, first, summary, n):
+    def __init__(self, counter, seg_off, first, summary, n, inserted=None):
         self._bc = counter
+        self.inserted = None if inserted is None else np.asarray(inserted, np.int64).reshape(-1, 2)
         self.seg_off = np.asarray(seg_off, np.int64)
         self.first = np.asarray(first, np.int64)
         self.summary = np.asarray(summary, np.int64).reshape(-1, CONS_COLS)
@@ -261,14 +303,16 @@ class BaseCounter:
     def __exit__(self, *exc):
         self.close()
 
-    def begin(self, tids, starts, ends, min_baseq=0):
+    def begin(self, tids, starts, ends, min_baseq=0, insertions=False):
         """Allocates and zeroes the planes of the segments [start, end) of
-        contig tid; returns N, the positions in all."""
+        contig tid; returns N, the positions in all.  insertions: also collect
+        the reads' insertion alleles (insertions(), consensus(insertions=True))."""
         tids = np.ascontiguousarray(tids, dtype=np.int32)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
         ends = np.ascontiguousarray(ends, dtype=np.int64)
         if not len(tids) == len(starts) == len(ends):
             raise ValueError("tids / starts / ends lengths differ")
+        check(self._lib.mc_bases_track_insertions(self._h, int(bool(insertions))), self._lib)
         check(self._lib.mc_bases_begin(self._h, len(tids), ptr(tids), ptr(starts), ptr(ends), int(min_baseq)),
               self._lib)
         self._S = len(tids)
@@ -370,6 +414,42 @@ class BaseCounter:
         check(self._lib.mc_bases_sites_get(self._h, 0, n, ptr(pos), ptr(cnt)), self._lib)
         return Sites(first, pos, cnt)
 
+    def insertions(self, min_depth=1, min_count=1, min_ppm=0):
+        """The grouped insertion alleles (see the header, "Insertion alleles")
+        that pass the sites predicate with their own count; needs
+        begin(..., insertions=True).  Returns an Insertions."""
+        n = ctypes.c_int64()
+        check(self._lib.mc_bases_insertions(self._h, int(min_depth), int(min_count), int(min_ppm), ctypes.byref(n)),
+              self._lib)
+        n = n.value
+        first = np.zeros(self._S + 1, np.int64)
+        check(self._lib.mc_bases_insertions_first(self._h, ptr(first)), self._lib)
+        index, length, code = np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.uint64)
+        other, count = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        check(self._lib.mc_bases_insertions_get(self._h, 0, n, ptr(index), ptr(length), ptr(code), ptr(other),
+                                                ptr(count)), self._lib)
+        return Insertions(first, index, length, code, other, count)
+
+    def set_insertions(self, index, length, code, other, count):
+        """Test hook (mc_bases_ins_set): installs a grouped allele table, rows
+        sorted by (index, other, length, code) and unique, in place of the
+        reads' events."""
+        index = np.ascontiguousarray(index, dtype=np.int64)
+        length = np.ascontiguousarray(length, dtype=np.int32)
+        code = np.ascontiguousarray(code, dtype=np.uint64)
+        other = np.ascontiguousarray(other, dtype=np.uint8)
+        count = np.ascontiguousarray(count, dtype=np.uint32)
+        if not len(index) == len(length) == len(code) == len(other) == len(count):
+            raise ValueError("row arrays of inconsistent length")
+        check(self._lib.mc_bases_ins_set(self._h, len(index), ptr(index), ptr(length), ptr(code), ptr(other),
+                                         ptr(count)), self._lib)
+
+    def insertions_timing(self):
+        a, b, c, n = ctypes.c_float(), ctypes.c_float(), ctypes.c_float(), ctypes.c_int64()
+        check(self._lib.mc_bases_insertions_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                   ctypes.byref(n)), self._lib)
+        return {"extract_ms": a.value, "group_ms": b.value, "consensus_ms": c.value, "events": n.value}
+
     def set_counts(self, first, planes):
         """Test hook (mc_bases_set): overwrites plane indices first .. first +
         count with planes, uint32 [6, count]; sites and consensus results are
@@ -379,15 +459,18 @@ class BaseCounter:
             raise ValueError("planes must be [6, count]")
         check(self._lib.mc_bases_set(self._h, int(first), planes.shape[1], ptr(planes)), self._lib)
 
-    def consensus(self, min_depth=1, min_count=1, call_ppm=0, iupac=False, fill_ref=False, ref=None):
+    def consensus(self, min_depth=1, min_count=1, call_ppm=0, iupac=False, fill_ref=False, ref=None,
+                  insertions=False):
         """One letter per position, called on the device (see the header,
         "Consensus"); ref: optional uint8 [N] codes as sites takes them.
+        insertions: the called insertion alleles follow their anchor's letter
+        in the compact output (needs begin(..., insertions=True)).
         Returns a Consensus; its letters stay on the device until fetched."""
         if ref is not None:
             ref = np.ascontiguousarray(ref, dtype=np.uint8)
             if len(ref) != int(self.seg_off[-1]):
                 raise ValueError("the reference plane must have one entry per position")
-        flags = (CONS_IUPAC if iupac else 0) | (CONS_FILL_REF if fill_ref else 0)
+        flags = (CONS_IUPAC if iupac else 0) | (CONS_FILL_REF if fill_ref else 0) | (CONS_INS if insertions else 0)
         n = ctypes.c_int64()
         # (an empty plane still counts as given: FILL_REF with N == 0 is valid)
         p = None if ref is None else ctypes.c_void_p(ref.ctypes.data)
@@ -397,7 +480,11 @@ class BaseCounter:
         check(self._lib.mc_bases_consensus_first(self._h, ptr(first)), self._lib)
         summary = np.zeros((self._S, CONS_COLS), np.int64)
         check(self._lib.mc_bases_consensus_summary(self._h, ptr(summary)), self._lib)
-        return Consensus(self, self.seg_off, first, summary, n.value)
+        inserted = None
+        if insertions:
+            inserted = np.zeros((self._S, 2), np.int64)
+            check(self._lib.mc_bases_consensus_ins(self._h, ptr(inserted)), self._lib)
+        return Consensus(self, self.seg_off, first, summary, n.value, inserted)
 
     def consensus_letters(self, compact, first, count):
         """uint8 [count] of the aligned (compact false) or compact letters,
@@ -488,6 +575,21 @@ def write_sites(fh, name, pos, counts, ref=None):
     return n
 
 
+INSERTIONS_HEADER = "contig\tpos\tdepth\tcount\tlen\tseq\n"
+
+
+def write_insertions(fh, name, pos, depth, count, length, seqs):
+    """Tab-separated `contig pos depth count len seq` lines of one contig:
+    pos [n] 0-based anchors (written 1-based, as write_sites), depth the
+    anchor's A + C + G + T + DEL, seqs the inserted bases ('*' with len 0 for
+    the OTHER row).  Returns the lines written."""
+    n = len(pos)
+    for k in range(n):
+        fh.write("%s\t%d\t%d\t%d\t%d\t%s\n" % (name, int(pos[k]) + 1, int(depth[k]), int(count[k]),
+                                               int(length[k]), seqs[k]))
+    return n
+
+
 # --------------------------------------------------------------- consensus
 
 SUMMARY_HEADER = "contig\tstart\tend\t" + "\t".join(SUMMARY_COLUMNS) + "\n"
@@ -517,27 +619,37 @@ def write_fasta(fh, name, letters, width=60):
     fh.write(out.tobytes().decode("ascii"))
 
 
-def write_consensus_summary(fh, names, starts, ends, summary, header=True):
+SUMMARY_HEADER_INS = SUMMARY_HEADER[:-1] + "\tinsertions\tinserted\n"
+
+
+def write_consensus_summary(fh, names, starts, ends, summary, header=True, inserted=None):
     """Tab-separated `contig start end positions called ambiguous nocall low
     deleted differs length`, one line per segment (start, end 0-based,
-    half-open); returns the lines written."""
+    half-open); inserted (Consensus.inserted): two trailing columns
+    `insertions inserted`.  Returns the lines written."""
     if header:
-        fh.write(SUMMARY_HEADER)
+        fh.write(SUMMARY_HEADER if inserted is None else SUMMARY_HEADER_INS)
     summary = np.asarray(summary, np.int64).reshape(-1, CONS_COLS)
+    if inserted is not None:
+        summary = np.concatenate([summary, np.asarray(inserted, np.int64).reshape(-1, 2)], axis=1)
     for name, a, b, row in zip(names, starts, ends, summary.tolist()):
         fh.write("%s\t%d\t%d\t%s\n" % (name, int(a), int(b), "\t".join(str(v) for v in row)))
     return len(summary)
 
 
 def consensus(path, contig, start=None, stop=None, quality_threshold=0, min_mapq=0, min_depth=1, min_count=1,
-              call_ppm=0, iupac=False, fill_ref=False, ref=None, aligned=False, device=0, decode="host"):
+              call_ppm=0, iupac=False, fill_ref=False, ref=None, aligned=False, device=0, decode="host",
+              insertions=False):
     """The consensus of [start, stop) of one contig (default: all of it) in
     one call: (letters uint8, summary int64 [8]).  aligned: keep '-' for the
     deleted positions, one letter per reference position.  ref: optional
     ASCII letters (str, bytes or uint8) of the same range.  decode: as
-    add_bam."""
+    add_bam.  insertions: the compact letters include the called insertion
+    alleles (not with aligned: that output has one letter per position)."""
     if decode not in ("host", "gpu"):
         raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
+    if insertions and aligned:
+        raise ValueError("insertions has no place in the aligned output")
     lib = _lib.load()
     with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
         names = [w.split()[0] if w.split() else w for w in src.references]
@@ -557,7 +669,7 @@ def consensus(path, contig, start=None, stop=None, quality_threshold=0, min_mapq
         if len(codes) != stop - start:
             raise ValueError("ref must have stop - start letters")
     with BaseCounter(len(names), device, lib) as bc:
-        bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
+        bc.begin([tid], [start], [stop], min_baseq=quality_threshold, insertions=insertions)
         bc.add_bam(path, min_mapq=min_mapq, decode=decode)
-        c = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes)
+        c = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes, insertions=insertions)
         return (c.aligned(0) if aligned else c.compact(0)), c.summary[0].copy()

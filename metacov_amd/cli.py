@@ -753,16 +753,20 @@ def _segment_letters(fa, name, start, end):
 
 
 def write_bases(path, references, tids, starts, ends, outfile, fasta=None, device=0, min_baseq=0, min_mapq=0,
-                min_depth=1, min_count=1, min_ppm=0, every=False, decode="host"):
+                min_depth=1, min_count=1, min_ppm=0, every=False, decode="host", insertions=None):
     """The base-count table of the segments (header contig ids), group by
     group, each written before the next is computed.  decode "host": each
     group is one pass over the BAM on host threads; "gpu": the file is decoded
-    once on the device and every group reads the resident records.  Returns
-    (lines written, the source's record counts)."""
+    once on the device and every group reads the resident records.
+    insertions: a text file for the insertion alleles that pass the same
+    thresholds with their own count (`contig pos depth count len seq`).
+    Returns (lines written, the source's record counts)."""
     from . import bases as _bases
     import contextlib
     names = [w.split()[0] if w.split() else w for w in references]
     outfile.write(_bases.HEADER)
+    if insertions is not None:
+        insertions.write(_bases.INSERTIONS_HEADER)
     written, counts = 0, None
     if len(tids) == 0:
         return 0, None
@@ -779,13 +783,16 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
                                                "run with --decode host (%s)" % (path, device, e))
                 raise
         for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
-            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
+            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions is not None)
             if src is not None:
                 bc.add_device(src)
                 counts = src.counts()
             else:
                 counts = bc.add_bam(path, min_mapq=min_mapq)
             seg_off = bc.seg_off
+            if insertions is not None:
+                _write_insertions(bc, names, tids[a:b], starts[a:b], seg_off, min_depth, min_count, min_ppm,
+                                  insertions)
             letters = None
             if fa is not None:
                 letters = np.concatenate([_segment_letters(fa, names[int(tids[i])], starts[i], ends[i])
@@ -810,6 +817,29 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
     return written, counts
 
 
+def _write_insertions(bc, names, tids, starts, seg_off, min_depth, min_count, min_ppm, fh):
+    """The insertion rows of the counter's current segments, in segment and
+    position order; the depth column from the planes, fetched over the span of
+    at most GET_CHUNK positions that a run of rows covers.  Returns the lines."""
+    from . import bases as _bases
+    ins = bc.insertions(min_depth, min_count, min_ppm)
+    written = 0
+    for i in range(len(tids)):
+        r0, r1 = int(ins.first[i]), int(ins.first[i + 1])
+        while r0 < r1:
+            lo = int(ins.index[r0])
+            r2 = r0 + int(np.searchsorted(ins.index[r0:r1], lo + _bases.GET_CHUNK))
+            hi = int(ins.index[r2 - 1]) + 1
+            planes = bc.counts(lo, hi - lo).astype(np.int64)
+            depth = planes[[_bases.A, _bases.C, _bases.G, _bases.T, _bases.DEL]].sum(axis=0)
+            idx = ins.index[r0:r2]
+            written += _bases.write_insertions(fh, names[int(tids[i])], idx - int(seg_off[i]) + int(starts[i]),
+                                               depth[idx - lo], ins.count[r0:r2], ins.length[r0:r2],
+                                               [ins.sequence(k) for k in range(r0, r2)])
+            r0 = r2
+    return written
+
+
 @main.command()
 @click.option('--bamfile', '-b', type=click.File('rb'), required=True,
               help="Input BAM file. Must be coordinate-sorted.")
@@ -818,6 +848,10 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
 @click.option('--reference-fasta', '-f', type=click.File('rb'),
               help="Reference FASTA (plain or gzip): fills the ref column and makes the reference base "
                    "the base allele")
+@click.option('--insertions', type=click.File('w'), metavar="FILE",
+              help="Also write the insertion alleles `contig pos depth count len seq` (pos: the base before "
+                   "the inserted ones; seq `*`: longer than 32 or with an ambiguity code) that pass "
+                   "--min-depth, --min-count and --min-frac with their own count")
 @click.option('--regionfile-blast7', '-rb', type=click.File('r'),
               help="Input Region file in BLAST7 format")
 @click.option('--regionfile-csv', '-rc', type=click.File('r'),
@@ -838,8 +872,8 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
 @click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
               help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
                    "the GPU, the records staying in device memory (the file's reads must fit there)")
-def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, min_baseq, min_mapq, min_depth,
-          min_count, min_frac, every, device, decode):
+def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regionfile_csv, min_baseq, min_mapq,
+          min_depth, min_count, min_frac, every, device, decode):
     """
     Write per-position base counts and variant sites
 
@@ -875,8 +909,10 @@ def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, 
         ends = np.asarray(lengths, np.int64)
     n, counts = write_bases(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
                             min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth, min_count=min_count,
-                            min_ppm=min_ppm, every=every, decode=decode)
+                            min_ppm=min_ppm, every=every, decode=decode, insertions=insertions)
     outfile.flush()
+    if insertions is not None:
+        insertions.flush()
     if counts:
         log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
                  "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
@@ -887,16 +923,20 @@ def bases(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, 
 
 def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta=None, device=0, min_baseq=0,
                     min_mapq=0, min_depth=1, min_count=1, call_ppm=0, iupac=False, fill_ref=False, aligned=False,
-                    summary=None, line_width=60, decode="host"):
+                    summary=None, line_width=60, decode="host", insertions=False):
     """One FASTA record per segment (header contig ids, record names
     `labels`), group by group as write_bases does it, each written before the
-    next is computed; `summary`: also the per-segment table.  Returns
-    (records written, the source's record counts)."""
+    next is computed; `summary`: also the per-segment table.  insertions: the
+    called insertion alleles are part of the letters (not with aligned) and
+    the table has two more columns.  Returns (records written, the source's
+    record counts)."""
     from . import bases as _bases
     import contextlib
+    if insertions and aligned:
+        raise ValueError("insertions has no place in the aligned output")
     names = [w.split()[0] if w.split() else w for w in references]
     if summary is not None:
-        summary.write(_bases.SUMMARY_HEADER)
+        summary.write(_bases.SUMMARY_HEADER_INS if insertions else _bases.SUMMARY_HEADER)
     counts = None
     if len(tids) == 0:
         return 0, None
@@ -913,7 +953,7 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
                                                "run with --decode host (%s)" % (path, device, e))
                 raise
         for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
-            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
+            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions)
             if src is not None:
                 bc.add_device(src)
                 counts = src.counts()
@@ -924,13 +964,13 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
                 codes = _bases.ref_codes(np.concatenate(
                     [_segment_letters(fa, names[int(tids[i])], starts[i], ends[i]) for i in range(a, b)] +
                     [np.zeros(0, np.uint8)]))
-            cons = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes)
+            cons = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes, insertions=insertions)
             for i in range(a, b):
                 _bases.write_fasta(outfile, labels[i], cons.aligned(i - a) if aligned else cons.compact(i - a),
                                    line_width)
             if summary is not None:
                 _bases.write_consensus_summary(summary, [names[int(t)] for t in tids[a:b]], starts[a:b], ends[a:b],
-                                               cons.summary, header=False)
+                                               cons.summary, header=False, inserted=cons.inserted)
     return len(tids), counts
 
 
@@ -961,9 +1001,12 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
               help="Write the reference base in lower case where the depth is below --min-depth (needs -f)")
 @click.option('--aligned', is_flag=True, default=False,
               help="Keep deleted positions as `-`: one letter per reference position, reference coordinates")
+@click.option('--insertions', is_flag=True, default=False,
+              help="Write the called insertion (per position the most frequent one of at most 32 bases, if it "
+                   "passes --min-count and --call-frac) behind its position's letter; not with --aligned")
 @click.option('--summary', type=click.File('w'), metavar="FILE",
               help="Also write `contig start end positions called ambiguous nocall low deleted differs length` "
-                   "per record")
+                   "per record (with --insertions two more columns: insertions, inserted)")
 @click.option('--line-width', type=click.IntRange(0), default=60, show_default=True,
               help="Letters per FASTA line; 0: no wrap")
 @click.option('--device', type=int, default=0, help="HIP device ordinal")
@@ -971,7 +1014,7 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
               help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
                    "the GPU, the records staying in device memory (the file's reads must fit there)")
 def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, min_baseq, min_mapq, min_depth,
-              min_count, call_frac, iupac, fill_ref, aligned, summary, line_width, device, decode):
+              min_count, call_frac, iupac, fill_ref, aligned, insertions, summary, line_width, device, decode):
     """
     Write the consensus sequence of the reads as FASTA
 
@@ -980,8 +1023,10 @@ def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_c
     inclusive).  Per position the allele with the highest count among A, C, G,
     T and deletion is called if it passes --min-count and --call-frac; a
     called deletion is left out (or `-` with --aligned), anything else is N.
-    The consensus never contains inserted bases: insertions in the reads are
-    not counted.  Called on the GPU; single process only.
+    Without --insertions the consensus never contains inserted bases; with
+    it the most frequent insertion after a position, if it passes the same two
+    thresholds, follows that position's letter.  Called on the GPU; single
+    process only.
     """
     from . import bases as _bases
     if regionfile_blast7 and regionfile_csv:
@@ -990,6 +1035,9 @@ def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_c
         raise click.BadParameter("must lie in [0, 1]", param_hint="--call-frac")
     if fill_ref and not reference_fasta:
         raise click.BadParameter("needs a reference (-f)", param_hint="--fill-ref")
+    if insertions and aligned:
+        raise click.BadParameter("the aligned output has one letter per reference position and no place for "
+                                 "inserted bases", param_hint="--insertions")
     call_ppm = int(round(call_frac * 1e6))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise click.UsageError("consensus runs in one process (WORLD_SIZE > 1 is not supported: "
@@ -1011,7 +1059,8 @@ def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_c
     n, counts = write_consensus(bamfile.name, references, tids, starts, ends, labels, outfile, fasta=fasta,
                                 device=device, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
                                 min_count=min_count, call_ppm=call_ppm, iupac=iupac, fill_ref=fill_ref,
-                                aligned=aligned, summary=summary, line_width=line_width, decode=decode)
+                                aligned=aligned, summary=summary, line_width=line_width, decode=decode,
+                                insertions=insertions)
     outfile.flush()
     if summary is not None:
         summary.flush()

@@ -47,6 +47,9 @@
 //                         reads the total (8 bytes) between scan and emit.
 //   cons_call / scan / emit     the consensus letters (see the kernels): the
 //                         same pattern, the emit over the 1-byte letters.
+//   ins_* / cons_ins_*    the opt-in insertion stage (bases_ins.h): events per
+//                         batch behind the pileup launch, grouped into the
+//                         allele table, called into the compact consensus.
 //
 // A tile whose first plane index is not 16-byte aligned starts `lead` (1..3)
 // elements into its LDS window and holds at most kTile - lead positions, so
@@ -591,6 +594,8 @@ __global__ __launch_bounds__(kThreads) void cons_emit_kernel(const uint8_t* __re
     }
 }
 
+#include "bases_ins.h"   // the insertion stage's kernels
+
 }  // namespace
 
 #define HIP_TRY(expr)                                                          \
@@ -627,6 +632,19 @@ struct Buf {
     }
 };
 
+// a grouped allele table in device memory (rows sorted by (i, other, len, code))
+struct InsTable {
+    Buf<int64_t> i;
+    Buf<int32_t> len;
+    Buf<uint64_t> code;
+    Buf<uint8_t> other;
+    Buf<uint32_t> cnt;
+    Buf<int32_t> rowcount;               // [T]
+    Buf<int64_t> rowbase, first;         // [T + 1], [S + 1]
+    int64_t n = 0;
+    bool valid = false;
+};
+
 }  // namespace
 
 struct mc_bases {
@@ -634,7 +652,8 @@ struct mc_bases {
     int32_t n_ref = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned long long* pin = nullptr;   // [0] lowest bad read, [1] max span (int32), [2] site total
+    unsigned long long* pin = nullptr;   // [0] lowest bad read, [1] max span (int32), [2] site total, [3] consensus
+                                         // total, [4] insertion totals (8 words in all)
     // segments and planes (mc_bases_begin)
     bool begun = false;
     int32_t min_baseq = 0;
@@ -670,7 +689,29 @@ struct mc_bases {
     Buf<int32_t> cons_cols;              // [8][T]
     Buf<int64_t> cons_pre, cons_first, cons_rows;   // [8][T + 1], [S + 1], [S][8]
     float ms_cons_call = 0, ms_cons_scan = 0, ms_cons_emit = 0;
+    // insertions (opt-in, mc_bases_track_insertions): events, their sorted buckets, two row tables
+    bool track_next = false, tracking = false;
+    bool ins_from_set = false;           // mc_bases_ins_set installed the sorted buckets
+    int64_t n_events = 0;
+    InsEvent* events = nullptr;          // grows with its contents kept
+    size_t events_cap = 0;
+    std::vector<int64_t> tile_out;       // the tiles' first plane indices, on the host (mc_bases_ins_set)
+    Buf<int32_t> ins_counts, tile_total, ins_cursor;
+    Buf<int64_t> ins_base, ins_bbase;
+    bool sorted_valid = false, have_weight = false;
+    Buf<InsEvent> ins_sorted;
+    Buf<uint32_t> ins_weight;
+    InsTable tab_user, tab_cons;
+    Buf<uint8_t> cons_called;
+    Buf<int32_t> cons_ins_cols;          // [2][T]: bases inserted, insertions called
+    Buf<int64_t> cons_ins_pre, cons_ins_first, cons_ins_rows;   // [2][T + 1], [2][S + 1], [S][2]
+    bool have_cons_ins = false;
+    hipEvent_t iev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float ms_ins_extract = 0, ms_ins_group = 0, ms_ins_cons = 0;
     ~mc_bases() {
+        for (auto& e : iev)
+            if (e) (void)hipEventDestroy(e);
+        if (events) (void)hipFree(events);
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto& e : cev)
@@ -692,10 +733,11 @@ extern "C" int mc_bases_create(int device, int32_t n_ref, mc_bases** out) {
     h->device = device;
     h->n_ref = n_ref;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipHostMalloc((void**)&h->pin, 4 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
+              hipHostMalloc((void**)&h->pin, 8 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
               h->flags.reserve(2) == hipSuccess;
     for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     for (auto& e : h->cev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (auto& e : h->iev) ok = ok && hipEventCreate(&e) == hipSuccess;
     if (!ok) {
         delete h;
         mc::set_error("HIP stream / event creation failed");
@@ -727,6 +769,8 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->begun = false;
     h->have_sites = false;
     h->have_cons = false;
+    h->have_cons_ins = false;
+    h->tracking = false;
 
     // ---- tile table (host): a tile never spans two segments
     std::vector<Tile> tiles;
@@ -779,7 +823,22 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     if (T) HIP_TRY(hipMemcpyAsync(h->order.p, order.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->seg_tile.p, seg_tile.data(), ((size_t)S + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(h->planes.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
+    if (h->track_next) {                          // the events of an earlier begin are gone
+        HIP_TRY(h->tile_total.reserve((size_t)T));
+        if (T) HIP_TRY(hipMemsetAsync(h->tile_total.p, 0, (size_t)T * 4, st));
+    }
     HIP_TRY(hipStreamSynchronize(st));            // the host vectors are released
+    h->tracking = h->track_next;
+    h->n_events = 0;
+    h->ins_from_set = false;
+    h->sorted_valid = h->have_weight = false;
+    h->tab_user.valid = h->tab_cons.valid = false;
+    h->ms_ins_extract = h->ms_ins_group = h->ms_ins_cons = 0;
+    h->tile_out.clear();
+    if (h->tracking) {
+        h->tile_out.resize((size_t)T);
+        for (int64_t i = 0; i < T; ++i) h->tile_out[(size_t)i] = tiles[(size_t)i].out;
+    }
     h->S = S;
     h->N = N;
     h->stride = stride;
@@ -825,6 +884,138 @@ void name_bad_read(const mc_bases* h, int64_t i, const int32_t* tid, const int32
     mc::set_error("read %lld: reference span %lld exceeds 2^31 - 1", r, (long long)ref);
 }
 
+constexpr int64_t kMaxEvents = INT32_MAX;   // per begin: every count and prefix of the stage fits 31 bits
+
+// The events table with room for `need` events, the first n_events kept.
+int ins_reserve_events(mc_bases* h, size_t need) {
+    if (need <= h->events_cap) return MC_OK;
+    const size_t want = std::max({need, h->events_cap * 2, (size_t)4096});
+    InsEvent* p = nullptr;
+    HIP_TRY(hipMalloc(&p, want * sizeof(InsEvent) + kArenaPad));
+    if (h->events && h->n_events) {
+        const hipError_t e = hipMemcpyAsync(p, h->events, (size_t)h->n_events * sizeof(InsEvent),
+                                            hipMemcpyDeviceToDevice, h->stream);
+        if (e != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+            (void)hipFree(p);
+            mc::set_error("copying the insertion events failed");
+            return MC_E_HIP;
+        }
+    }
+    if (h->events) (void)hipFree(h->events);
+    h->events = p;
+    h->events_cap = want;
+    return MC_OK;
+}
+
+// The insertion events of the batch in flight, behind its pileup launch: the
+// same tiles (nt of them from index first of the sorted order).  The batch
+// total comes back on the synchronisation that ends the batch anyway; a batch
+// with events costs one more for its fill pass.
+int ins_extract(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span) {
+    hipStream_t st = h->stream;
+    h->tab_user.valid = h->tab_cons.valid = false;
+    h->have_cons_ins = false;
+    HIP_TRY(h->ins_counts.reserve((size_t)nt));
+    HIP_TRY(h->ins_base.reserve((size_t)nt + 1));
+    HIP_TRY(hipEventRecord(h->iev[0], st));
+    hipLaunchKernelGGL(ins_extract_kernel<false>, dim3((unsigned)nt), dim3(kThreads), 0, st, b, h->span.p, h->tiles.p,
+                       h->order.p + first, max_span, h->ins_counts.p, (const int64_t*)nullptr, (InsEvent*)nullptr,
+                       (int64_t)0, (int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->ins_counts.p, nt, h->ins_base.p,
+                       (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->pin + 4, h->ins_base.p + nt, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int64_t total = 0;
+    std::memcpy(&total, h->pin + 4, 8);
+    MC_REQUIRE(total >= 0, MC_E_STATE, "insertion event count %lld out of range", (long long)total);
+    MC_REQUIRE(h->n_events + total <= kMaxEvents, MC_E_RANGE, "more than 2^31 - 1 insertion events");
+    if (total) {
+        const int rc = ins_reserve_events(h, (size_t)(h->n_events + total));
+        if (rc != MC_OK) return rc;
+        hipLaunchKernelGGL(ins_extract_kernel<true>, dim3((unsigned)nt), dim3(kThreads), 0, st, b, h->span.p,
+                           h->tiles.p, h->order.p + first, max_span, h->ins_counts.p, h->ins_base.p,
+                           h->events + h->n_events, total, h->tile_total.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->iev[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, h->iev[0], h->iev[1]));
+    h->ms_ins_extract += ms;
+    h->n_events += total;
+    h->sorted_valid = false;
+    return MC_OK;
+}
+
+// The events in per-tile buckets, each sorted by (i, other, len, code); kept
+// until the events change.
+int ins_sort(mc_bases* h) {
+    if (h->sorted_valid) return MC_OK;
+    const int64_t T = h->n_tiles, E = h->n_events;
+    hipStream_t st = h->stream;
+    HIP_TRY(h->ins_bbase.reserve((size_t)T + 1));
+    HIP_TRY(h->ins_cursor.reserve((size_t)T));
+    HIP_TRY(h->ins_sorted.reserve((size_t)E));
+    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->tile_total.p, T, h->ins_bbase.p,
+                       (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    if (E && T) {
+        HIP_TRY(hipMemsetAsync(h->ins_cursor.p, 0, (size_t)T * 4, st));
+        hipLaunchKernelGGL(ins_scatter_kernel, dim3((unsigned)((E + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                           h->events, E, T, h->ins_bbase.p, h->ins_cursor.p, h->ins_sorted.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(ins_sort_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->ins_sorted.p, h->ins_bbase.p,
+                           h->tiles.p);
+        HIP_TRY(hipGetLastError());
+    }
+    h->have_weight = false;
+    h->sorted_valid = true;
+    return MC_OK;
+}
+
+// The rows of the sorted buckets that pass the thresholds, into tab.
+int ins_encode(mc_bases* h, const SiteArgs& sa, InsTable& tab) {
+    const int64_t T = h->n_tiles, S = h->S;
+    hipStream_t st = h->stream;
+    tab.valid = false;
+    HIP_TRY(tab.rowcount.reserve((size_t)T));
+    HIP_TRY(tab.rowbase.reserve((size_t)T + 1));
+    HIP_TRY(tab.first.reserve((size_t)S + 1));
+    const uint32_t* w = h->have_weight ? h->ins_weight.p : nullptr;
+    if (T) {
+        hipLaunchKernelGGL(ins_encode_kernel<false>, dim3((unsigned)T), dim3(kThreads), 0, st, h->ins_sorted.p, w,
+                           h->ins_bbase.p, h->planes.p, h->stride, sa, tab.rowcount.p, (const int64_t*)nullptr,
+                           (int64_t*)nullptr, (int32_t*)nullptr, (uint64_t*)nullptr, (uint8_t*)nullptr,
+                           (uint32_t*)nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, tab.rowcount.p, T, tab.rowbase.p,
+                       h->seg_tile.p, S, tab.first.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->pin + 4, tab.rowbase.p + T, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int64_t total = 0;
+    std::memcpy(&total, h->pin + 4, 8);
+    MC_REQUIRE(total >= 0 && total <= h->n_events, MC_E_STATE, "insertion row count %lld out of range",
+               (long long)total);
+    HIP_TRY(tab.i.reserve((size_t)total));
+    HIP_TRY(tab.len.reserve((size_t)total));
+    HIP_TRY(tab.code.reserve((size_t)total));
+    HIP_TRY(tab.other.reserve((size_t)total));
+    HIP_TRY(tab.cnt.reserve((size_t)total));
+    if (T && total) {
+        hipLaunchKernelGGL(ins_encode_kernel<true>, dim3((unsigned)T), dim3(kThreads), 0, st, h->ins_sorted.p, w,
+                           h->ins_bbase.p, h->planes.p, h->stride, sa, (int32_t*)nullptr, tab.rowbase.p, tab.i.p,
+                           tab.len.p, tab.code.p, tab.other.p, tab.cnt.p);
+        HIP_TRY(hipGetLastError());
+    }
+    tab.n = total;
+    tab.valid = true;
+    return MC_OK;
+}
+
 }  // namespace
 
 extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
@@ -833,6 +1024,7 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
                                   const uint8_t* qual) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
     MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
     if (n == 0) return MC_OK;
     MC_REQUIRE(tid && pos && cig_off && l_seq && seq_off && qual_off, MC_E_INVALID, "null read arrays");
@@ -907,6 +1099,10 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[3], st));
+    if (h->tracking && max_span > 0 && t_lo < t_hi) {
+        const int rc = ins_extract(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span);
+        if (rc != MC_OK) return rc;
+    }
     HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays and the handle's batch buffers are free again
     float a = 0, c = 0;
     HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
@@ -919,6 +1115,8 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     h->n_reads += n;
     h->have_sites = false;
     h->have_cons = false;
+    h->have_cons_ins = false;
+    h->tab_user.valid = h->tab_cons.valid = false;
     return MC_OK;
 }
 
@@ -944,6 +1142,7 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
                                          int64_t qual_bytes) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
     MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
     if (n == 0) return MC_OK;
     MC_REQUIRE(d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off, MC_E_INVALID, "null read arrays");
@@ -1026,6 +1225,10 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[3], st));
+    if (h->tracking && max_span > 0 && t_lo < t_hi) {
+        const int rc = ins_extract(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span);
+        if (rc != MC_OK) return rc;
+    }
     HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays are free again
     float a = 0, c = 0;
     HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
@@ -1038,6 +1241,8 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
     h->n_reads += n;
     h->have_sites = false;
     h->have_cons = false;
+    h->have_cons_ins = false;
+    h->tab_user.valid = h->tab_cons.valid = false;
     return MC_OK;
 }
 
@@ -1171,6 +1376,8 @@ extern "C" int mc_bases_set(mc_bases* h, int64_t first, int64_t count, const uin
     MC_REQUIRE(count == 0 || in, MC_E_INVALID, "null in");
     h->have_sites = false;
     h->have_cons = false;
+    h->have_cons_ins = false;
+    h->tab_user.valid = h->tab_cons.valid = false;      // (their rows were kept by depth)
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
     for (int c = 0; c < kPlanes; ++c)
@@ -1187,10 +1394,14 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
     MC_REQUIRE(min_depth >= 0 && min_count >= 0 && call_ppm >= 0 && call_ppm <= 1000000, MC_E_INVALID,
                "consensus thresholds out of range (min_depth %lld, min_count %lld, call_ppm %lld of 10^6)",
                (long long)min_depth, (long long)min_count, (long long)call_ppm);
-    MC_REQUIRE((flags & ~(MC_CONS_IUPAC | MC_CONS_FILL_REF)) == 0, MC_E_INVALID, "unknown consensus flags 0x%x",
-               flags);
+    // (a handle that does not track knows no MC_CONS_INS: the bit is as unknown there as it always was)
+    MC_REQUIRE((flags & ~(MC_CONS_IUPAC | MC_CONS_FILL_REF | (h->tracking ? MC_CONS_INS : 0u))) == 0, MC_E_INVALID,
+               "unknown consensus flags 0x%x%s", flags,
+               (flags & MC_CONS_INS) ? " (MC_CONS_INS needs mc_bases_track_insertions before begin)" : "");
     MC_REQUIRE(!(flags & MC_CONS_FILL_REF) || ref, MC_E_INVALID, "MC_CONS_FILL_REF needs a reference plane");
+    const bool with_ins = (flags & MC_CONS_INS) != 0;
     h->have_cons = false;
+    h->have_cons_ins = false;
     const int64_t T = h->n_tiles, S = h->S;
     const ConsArgs ca{(unsigned long long)std::max<int64_t>(min_depth, 1),
                       (unsigned long long)std::max<int64_t>(min_count, 1), (unsigned long long)call_ppm, flags};
@@ -1223,6 +1434,63 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
     int64_t total = 0;
     std::memcpy(&total, h->pin + 3, 8);
     MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "consensus length %lld out of range", (long long)total);
+    int64_t inserted = 0;
+    if (with_ins) {
+        // the rows that qualify at a position that is not LOW, the top allele of each position, the two
+        // per-tile columns (bases inserted, insertions called) and their prefixes
+        HIP_TRY(hipEventRecord(h->iev[4], st));
+        int rc = ins_sort(h);
+        if (rc != MC_OK) return rc;
+        rc = ins_encode(h, SiteArgs{ca.min_depth, ca.min_count, ca.call_ppm}, h->tab_cons);
+        if (rc != MC_OK) return rc;
+        InsTable& tb = h->tab_cons;
+        HIP_TRY(h->cons_called.reserve((size_t)tb.n));
+        HIP_TRY(h->cons_ins_cols.reserve((size_t)(2 * T)));
+        HIP_TRY(h->cons_ins_pre.reserve((size_t)(2 * (T + 1))));
+        HIP_TRY(h->cons_ins_first.reserve((size_t)(2 * (S + 1))));
+        HIP_TRY(h->cons_ins_rows.reserve((size_t)(2 * S)));
+        if (tb.n) HIP_TRY(hipMemsetAsync(h->cons_called.p, 0, (size_t)tb.n, st));
+        if (T) {
+            hipLaunchKernelGGL(cons_ins_pick_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, tb.rowbase.p, tb.i.p,
+                               tb.len.p, tb.other.p, tb.cnt.p, h->cons_called.p, h->cons_ins_cols.p,
+                               h->cons_ins_cols.p + T);
+            HIP_TRY(hipGetLastError());
+        }
+        for (int c = 0; c < 2; ++c) {
+            hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->cons_ins_cols.p + c * T, T,
+                               h->cons_ins_pre.p + c * (T + 1), h->seg_tile.p, S, h->cons_ins_first.p + c * (S + 1));
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(cons_ins_fix_kernel, dim3((unsigned)(S / 256 + 1)), dim3(256), 0, st, S,
+                           h->cons_ins_first.p, h->cons_ins_first.p + (S + 1), h->cons_first.p, h->cons_rows.p,
+                           h->cons_ins_rows.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(h->iev[5], st));
+        HIP_TRY(hipMemcpyAsync(h->pin + 4, h->cons_ins_pre.p + T, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        std::memcpy(&inserted, h->pin + 4, 8);
+        MC_REQUIRE(inserted >= 0 && inserted <= kMaxInsLen * tb.n, MC_E_STATE, "inserted bases %lld out of range",
+                   (long long)inserted);
+        HIP_TRY(hipEventElapsedTime(&h->ms_ins_cons, h->iev[4], h->iev[5]));
+        HIP_TRY(h->cons_compact.reserve((size_t)(total + inserted)));
+        HIP_TRY(hipEventRecord(h->cev[3], st));
+        if (T) {
+            hipLaunchKernelGGL(cons_emit_ins_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->cons_aligned.p,
+                               h->tiles.p, h->cons_pre.p + 7 * (T + 1), h->cons_ins_pre.p, tb.rowbase.p, tb.i.p,
+                               tb.len.p, tb.code.p, h->cons_called.p, h->cons_compact.p, total + inserted);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(h->cev[4], st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipEventElapsedTime(&h->ms_cons_call, h->cev[0], h->cev[1]));
+        HIP_TRY(hipEventElapsedTime(&h->ms_cons_scan, h->cev[1], h->cev[2]));
+        HIP_TRY(hipEventElapsedTime(&h->ms_cons_emit, h->cev[3], h->cev[4]));
+        h->n_cons = total + inserted;
+        h->have_cons = true;
+        h->have_cons_ins = true;
+        *n_out = h->n_cons;
+        return MC_OK;
+    }
     HIP_TRY(h->cons_compact.reserve((size_t)total));
     HIP_TRY(hipEventRecord(h->cev[3], st));
     if (T) {
@@ -1292,5 +1560,159 @@ extern "C" int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, floa
     *call_ms = h->ms_cons_call;
     *scan_ms = h->ms_cons_scan;
     *emit_ms = h->ms_cons_emit;
+    return MC_OK;
+}
+
+// ---- insertion alleles (the contract is the header's, "Insertion alleles") ----
+
+extern "C" int mc_bases_track_insertions(mc_bases* h, int on) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(on == 0 || on == 1, MC_E_INVALID, "on must be 0 or 1, not %d", on);
+    h->track_next = on != 0;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_insertions(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                                   int64_t* n_rows) {
+    MC_REQUIRE(h && n_rows, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->tracking, MC_E_STATE, "insertions are not tracked (call mc_bases_track_insertions before begin)");
+    MC_REQUIRE(min_depth >= 0 && min_count >= 0 && min_ppm >= 0 && min_ppm <= 1000000, MC_E_INVALID,
+               "insertion thresholds out of range (min_depth %lld, min_count %lld, min_ppm %lld of 10^6)",
+               (long long)min_depth, (long long)min_count, (long long)min_ppm);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const SiteArgs sa{(unsigned long long)min_depth, (unsigned long long)min_count, (unsigned long long)min_ppm};
+    HIP_TRY(hipEventRecord(h->iev[2], st));
+    int rc = ins_sort(h);
+    if (rc != MC_OK) return rc;
+    rc = ins_encode(h, sa, h->tab_user);
+    if (rc != MC_OK) return rc;
+    HIP_TRY(hipEventRecord(h->iev[3], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventElapsedTime(&h->ms_ins_group, h->iev[2], h->iev[3]));   // (the 8-byte read-back included)
+    *n_rows = h->tab_user.n;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_insertions_first(const mc_bases* h, int64_t* first) {
+    MC_REQUIRE(h && first, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->tracking && h->tab_user.valid, MC_E_STATE, "no insertions computed (call mc_bases_insertions)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(first, h->tab_user.first.p, ((size_t)h->S + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_insertions_get(const mc_bases* h, int64_t first, int64_t count, int64_t* i, int32_t* len,
+                                       uint64_t* code, uint8_t* other, uint32_t* cnt) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->tracking && h->tab_user.valid, MC_E_STATE, "no insertions computed (call mc_bases_insertions)");
+    const InsTable& t = h->tab_user;
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= t.n && count <= t.n - first, MC_E_INVALID,
+               "rows [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count,
+               (long long)t.n);
+    MC_REQUIRE(count == 0 || (i && len && code && other && cnt), MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    HIP_TRY(hipMemcpyAsync(i, t.i.p + first, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(len, t.len.p + first, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(code, t.code.p + first, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(other, t.other.p + first, (size_t)count, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(cnt, t.cnt.p + first, (size_t)count * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_insertions_timing(const mc_bases* h, float* extract_ms, float* group_ms, float* cons_ms,
+                                          int64_t* events) {
+    MC_REQUIRE(h && extract_ms && group_ms && cons_ms && events, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->tracking, MC_E_STATE, "insertions are not tracked (call mc_bases_track_insertions before begin)");
+    *extract_ms = h->ms_ins_extract;
+    *group_ms = h->ms_ins_group;
+    *cons_ms = h->ms_ins_cons;
+    *events = h->n_events;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const int32_t* len, const uint64_t* code,
+                                const uint8_t* other, const uint32_t* cnt) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->tracking, MC_E_STATE, "insertions are not tracked (call mc_bases_track_insertions before begin)");
+    MC_REQUIRE(n >= 0 && n <= kMaxEvents, MC_E_INVALID, "row count %lld out of range", (long long)n);
+    MC_REQUIRE(n == 0 || (i && len && code && other && cnt), MC_E_INVALID, "null row arrays");
+    const int64_t T = h->n_tiles;
+    std::vector<InsEvent> ev((size_t)n);
+    std::vector<int32_t> total((size_t)T, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        MC_REQUIRE(i[r] >= 0 && i[r] < h->N, MC_E_INVALID, "row %lld: index %lld outside [0, %lld)", (long long)r,
+                   (long long)i[r], (long long)h->N);
+        MC_REQUIRE(other[r] <= 1, MC_E_INVALID, "row %lld: other is %d", (long long)r, (int)other[r]);
+        if (other[r])
+            MC_REQUIRE(len[r] == 0 && code[r] == 0, MC_E_INVALID, "row %lld: an OTHER row has len 0 and code 0",
+                       (long long)r);
+        else
+            MC_REQUIRE(len[r] >= 1 && len[r] <= kMaxInsLen && (len[r] == 32 || (code[r] >> (2 * len[r])) == 0),
+                       MC_E_INVALID, "row %lld: len %d or code out of range", (long long)r, len[r]);
+        MC_REQUIRE(cnt[r] >= 1, MC_E_INVALID, "row %lld: count 0", (long long)r);
+        InsEvent e;
+        e.i = i[r];
+        e.lo = other[r] ? kInsOther : (uint32_t)len[r];
+        e.code = code[r];
+        const int64_t t = std::upper_bound(h->tile_out.begin(), h->tile_out.end(), i[r]) - h->tile_out.begin() - 1;
+        MC_REQUIRE(t >= 0 && t < T, MC_E_STATE, "row %lld: no tile", (long long)r);
+        e.tile = (uint32_t)t;
+        if (r > 0) {
+            const InsEvent& p = ev[(size_t)r - 1];
+            MC_REQUIRE(p.i < e.i || (p.i == e.i && (p.lo < e.lo || (p.lo == e.lo && p.code < e.code))), MC_E_INVALID,
+                       "row %lld: rows are not sorted by (i, other, len, code) and unique", (long long)r);
+        }
+        ev[(size_t)r] = e;
+        ++total[(size_t)t];
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    h->sorted_valid = false;
+    h->tab_user.valid = h->tab_cons.valid = false;
+    h->have_cons_ins = false;
+    h->have_cons = false;
+    HIP_TRY(h->ins_sorted.reserve((size_t)n));
+    HIP_TRY(h->ins_weight.reserve((size_t)n));
+    HIP_TRY(h->ins_bbase.reserve((size_t)T + 1));
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(h->ins_sorted.p, ev.data(), (size_t)n * sizeof(InsEvent), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->ins_weight.p, cnt, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    if (T) HIP_TRY(hipMemcpyAsync(h->tile_total.p, total.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->tile_total.p, T, h->ins_bbase.p,
+                       (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    h->n_events = n;
+    h->ins_from_set = true;
+    h->have_weight = true;
+    h->sorted_valid = true;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_consensus_ins(const mc_bases* h, int64_t* rows) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_cons && h->have_cons_ins, MC_E_STATE,
+               "no consensus with MC_CONS_INS computed (call mc_bases_consensus)");
+    MC_REQUIRE(h->S == 0 || rows, MC_E_INVALID, "null rows");
+    if (h->S == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(rows, h->cons_ins_rows.p, (size_t)h->S * 2 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_ins_dims(int32_t* sort_chunk, int32_t* max_len) {
+    MC_REQUIRE(sort_chunk && max_len, MC_E_INVALID, "null argument");
+    *sort_chunk = kSortChunk;
+    *max_len = kMaxInsLen;
     return MC_OK;
 }
