@@ -183,8 +183,52 @@ def counts_model(batches, tids, starts, ends, min_baseq=0):
     return seg_off, planes.astype(np.uint32)
 
 
+def int32_edge_case(P, seed=0):
+    """One read set at the edge of the int32 positions, for the tests of the
+    counts, sites, consensus and insertions (P: the tile size).  On tid 1:
+    short reads with pos in [2^31 - 3P, 2^31 - 1] (a 1M read at 2^31 - 1
+    among them), reads whose reference end crosses 2^31, three reads at
+    2 * 10^9 that skip 7 * (2^28 - 1) positions (their ends lie below 2^32)
+    and insertions anchored at 2^31 - 2, 2^31 - 1, 2^31 and on the last
+    position of a tile and the one after it.  On tids 0 and 2: ordinary reads
+    near position 0.  Returns (reads sorted by (tid, pos), segments, the same
+    segments in scrambled order, k: the reads [0, k) lie below (1, 2^31 - P))."""
+    rng = np.random.default_rng(seed)
+    H, t = 1 << 31, 1
+
+    def rd(tid, pos, cigar, p_n=.04):
+        n = query_length(cigar_words(cigar))
+        return (tid, int(pos), cigar, "".join(rng.choice(list("ACGTN"), size=n, p=[(1 - p_n) / 4] * 4 + [p_n])), 30)
+
+    seg_a = (t, H - 2 * P - 3, H + P + 5)             # the first segment: its tiles start at multiples of P from it
+    reads = [rd(t, p, "40M") for p in rng.integers(H - 3 * P, H - 39, size=60)]
+    reads += [rd(t, p, "30M2D8M") for p in rng.integers(H - 3 * P, H - 39, size=20)]
+    reads += [rd(t, H - 1, "1M"), rd(t, H - 1, "1M"), rd(t, H - 1, "1D"), rd(t, H - 1, "30M"), rd(t, H - 20, "60M"),
+              rd(t, H - 50, "100M"), rd(t, H - 50, "40M5D55M"), rd(t, H - 2 * P - 40, "50M")]
+    skip = "".join(["%dN" % ((1 << 28) - 1)] * 7)
+    far = [rd(t, 2_000_000_000, "10M" + skip + "10M"), rd(t, 2_000_000_003, "10M" + skip + "4M3I6M", 0),
+           rd(t, 2_000_000_005, "6M2I4M" + skip + "5M1D5M")]                 # (no N in the insertion: an allele)
+    reads += far
+    far_end = max(r[1] + ref_span(cigar_words(r[2])) for r in far)
+    assert H + (1 << 30) < far_end < (1 << 32)
+    for a in (H - 2, H - 1, H, seg_a[1] + P - 1, seg_a[1] + P, seg_a[1] + 2 * P - 1, seg_a[1] + 2 * P):
+        for _ in range(3):
+            n = int(rng.integers(1, 3))
+            reads.append(rd(t, a - 4, "5M%dI5M" % n))
+        reads.append(rd(t, a - 2, "3M2I"))             # a trailing insertion: the anchor is the read's last position
+    for tid in (0, 2):
+        for p in rng.integers(0, 300, size=40):
+            reads.append(rd(tid, p, str(rng.choice(["30M", "10M2I10M", "12M3D9M", "5S20M", "8M1I8M"]))))
+    reads.sort(key=lambda r: (r[0], r[1]))
+    assert max(r[1] for r in reads) == H - 1
+    segs = [seg_a, (t, far_end - P - 35, far_end + 5), (t, H - 1, H), (0, 0, 400), (2, 3, 350)]
+    k = sum(1 for r in reads if (r[0], r[1]) < (t, H - P))
+    return reads, segs, [segs[i] for i in (3, 1, 4, 0, 2)], k
+
+
 def counts_loop(batches, tids, starts, ends, min_baseq=0):
-    """The same, as a literal per-read, per-base loop."""
+    """The same, as a literal per-read, per-base loop (an N op moves the
+    reference cursor in one step: a read may skip 2^31 positions)."""
     if isinstance(batches, dict):
         batches = [batches]
     seg_off = seg_offsets(starts, ends)
@@ -202,6 +246,9 @@ def counts_loop(batches, tids, starts, ends, min_baseq=0):
             absent = l > 0 and int(b["qual"][qo]) == 0xFF
             for w in b["cigar"][int(b["cig_off"][i]):int(b["cig_off"][i + 1])]:
                 op, n = OPS[int(w) & 15] if (int(w) & 15) < 9 else "?", int(w) >> 4
+                if op == "N":
+                    rp += n
+                    continue
                 for _ in range(n):
                     if op in "M=X":
                         byte = int(b["seq"][so + q // 2])
@@ -213,8 +260,6 @@ def counts_loop(batches, tids, starts, ends, min_baseq=0):
                         q += 1
                     elif op == "D":
                         count(tid, rp, DEL)
-                        rp += 1
-                    elif op == "N":
                         rp += 1
                     elif op in "IS":
                         q += 1

@@ -95,6 +95,35 @@ def test_model_matches_loop(seed):
     assert np.array_equal(a[1], d[1])
 
 
+def test_model_at_the_int32_edge(lib_built):
+    """bases_model.int32_edge_case (the GPU tests' read set around 2^31 and
+    below 2^32): the numpy model against the literal loop, in one and in two
+    batches, and the positions the sites model reports."""
+    from metacov_amd import bases as mb
+    P = mb.dims()
+    reads, segs, scrambled, k = bm.int32_edge_case(P)
+    b = bm.make_batch(reads)
+    assert b["pos"].dtype == np.int32 and int(b["pos"].max()) == 2 ** 31 - 1 and 0 < k < bm.n_reads(b)
+    for sg in (segs, scrambled):
+        tids, starts, ends = (np.array(x, np.int64) for x in zip(*sg))
+        a = bm.counts_model(b, tids, starts, ends)
+        c = bm.counts_loop(b, tids, starts, ends)
+        assert np.array_equal(a[0], c[0]) and np.array_equal(a[1], c[1])
+        for s in range(len(sg)):                                          # every segment holds counts
+            assert a[1][:, a[0][s]:a[0][s + 1]].sum() > 0, sg[s]
+        d = bm.counts_model([bm.slice_batch(b, 0, k), bm.slice_batch(b, k, bm.n_reads(b))], tids, starts, ends)
+        assert np.array_equal(a[1], d[1])
+        first, pos, cnt = bm.sites_model(a[1], a[0], starts, 0, 0, 0)
+        assert pos.dtype == np.int64
+        assert np.array_equal(pos, np.concatenate([np.arange(x, y, dtype=np.int64) for x, y in zip(starts, ends)]))
+        first, pos, cnt = bm.sites_model(a[1], a[0], starts, 1, 1, 0)
+        assert pos.max() > 2 ** 31 + 2 ** 30 and (pos == 2 ** 31 - 1).sum() >= 2 and (pos < 400).any()
+        for s in range(len(sg)):
+            p = pos[first[s]:first[s + 1]]
+            assert ((p >= starts[s]) & (p < ends[s])).all() and (np.diff(p) > 0).all()
+            assert np.array_equal(cnt[first[s]:first[s + 1]].T, a[1][:, a[0][s] + p - starts[s]])
+
+
 def test_sites_model_by_hand():
     #            A   C   G   T   N  DEL
     cols = [(10,  0,  0,  0,  5,  0),      # no alt

@@ -37,6 +37,29 @@ def test_model_matches_loop(seed):
                 assert np.array_equal(g, w), kw
 
 
+def test_model_at_the_int32_edge(lib_built):
+    """The planes of bases_model.int32_edge_case (the GPU tests' read set
+    around 2^31 and below 2^32): the model against the loop, and the
+    segments' rows against the letters."""
+    from metacov_amd import bases as mb
+    from tests import bases_model as bm
+    reads, segs, scrambled, k = bm.int32_edge_case(mb.dims())
+    b = bm.make_batch(reads)
+    for sg in (segs, scrambled):
+        tids, starts, ends = (np.array(x, np.int64) for x in zip(*sg))
+        off, planes = bm.counts_model(b, tids, starts, ends)
+        for kw in (dict(), dict(min_depth=2, iupac=True, call_ppm=200000)):
+            for g, w in zip(cm.call(planes, **kw), cm.call_loop(planes, **kw)):
+                assert np.array_equal(g, w), kw
+            first, summary, aligned, compact = cm.consensus_model(planes, off, **kw)
+            assert np.array_equal(summary[:, 0], ends - starts) and first[-1] == len(compact)
+            assert np.array_equal(aligned, cm.call(planes, **kw)[0])
+            for s in range(len(sg)):
+                a = aligned[off[s]:off[s + 1]]
+                assert np.array_equal(compact[first[s]:first[s + 1]], a[a != ord("-")])
+                assert (a != ord("N")).any(), sg[s]                         # every segment has called letters
+
+
 def test_model_by_hand():
     assert len(cm.HAND) > 70
     seen = set()

@@ -368,6 +368,41 @@ def test_sites_tiles_and_segments(bc, P):
     check_sites(bc, planes, starts, (2, 2, 250000), ref)
 
 
+# ------------------------------------------------------------ the int32 edge
+
+def test_int32_edge(bc, P):
+    """Positions around 2^31 and reference ends below 2^32
+    (bases_model.int32_edge_case): the planes, seg_off and the sites with
+    their int64 positions, with the segments in two orders and the reads in
+    one batch and in two."""
+    H = 1 << 31
+    rng = np.random.default_rng(9)
+    reads, segs, scrambled, k = bm.int32_edge_case(P)
+    b = bm.make_batch(reads)
+    n = bm.n_reads(b)
+    assert int(b["pos"].max()) == H - 1 and b["pos"][k - 1] < H - P <= b["pos"][k] and b["tid"][k] == 1
+    for sg in (segs, scrambled):
+        planes = check(bc, b, sg).copy()
+        starts = [s[1] for s in sg]
+        for s in range(len(sg)):                                          # every segment holds counts
+            assert planes[:, bc.seg_off[s]:bc.seg_off[s + 1]].sum() > 0, sg[s]
+        got = check_sites(bc, planes, starts, (1, 1, 0))
+        assert got.pos.max() > H + (1 << 30) and (got.pos == H - 1).sum() >= 2 and (got.pos == H).sum() == 1
+        assert (got.pos < 400).any()
+        every = check_sites(bc, planes, starts, (0, 0, 0))
+        assert np.array_equal(every.pos, np.concatenate([np.arange(x, y, dtype=np.int64) for _, x, y in sg]))
+        ref = rng.integers(0, 5, size=planes.shape[1]).astype(np.uint8)
+        check_sites(bc, planes, starts, (1, 1, 0), ref)
+        check_sites(bc, planes, starts, (2, 2, 200000), ref)
+        two = check(bc, [bm.slice_batch(b, 0, k), bm.slice_batch(b, k, n)], sg)
+        assert np.array_equal(two, planes)
+    # min_baseq, and one read per batch around 2^31: every batch has its own maximum span and tile range
+    check(bc, b, segs, 31)
+    a = int(np.searchsorted(b["pos"][:n - 40], H - 60))
+    check(bc, [bm.slice_batch(b, 0, a)] + [bm.slice_batch(b, i, i + 1) for i in range(a, n - 40)] +
+          [bm.slice_batch(b, n - 40, n)], segs)
+
+
 # ----------------------------------------------------------------------- fuzz
 
 def random_cigar(rng, P):

@@ -111,6 +111,27 @@ def test_full_range_counts(bc, P):
     check(bc, planes, off, min_count=cm.M32 - 1, call_ppm=1000000)
 
 
+# ------------------------------------------------------------ the int32 edge
+
+def test_int32_edge(bc, P):
+    """The consensus of reads around 2^31 and with reference ends below 2^32
+    (bases_model.int32_edge_case), counted by the pileup kernel, with the
+    segments in two orders."""
+    reads, segs, scrambled, k = bm.int32_edge_case(P)
+    b = bm.make_batch(reads)
+    for sg in (segs, scrambled):
+        off = begin(bc, sg)
+        bc.add_reads(*bm.batch_args(b))
+        tids, starts, ends = (np.array(x, np.int64) for x in zip(*sg))
+        want_off, planes = bm.counts_model(b, tids, starts, ends)
+        assert np.array_equal(off, want_off) and np.array_equal(bc.counts(), planes)
+        got = check(bc, planes, off)
+        assert (got.summary[:, mb.CALLED] > 0).all()                       # every segment has called letters
+        check(bc, planes, off, min_depth=2, iupac=True, call_ppm=200000)
+        ref = np.random.default_rng(10).integers(0, 5, size=planes.shape[1]).astype(np.uint8)
+        check(bc, planes, off, min_depth=3, fill_ref=True, ref=ref)
+
+
 # ----------------------------------------------------------------- segments
 
 def test_segment_shapes(bc, P):

@@ -277,6 +277,37 @@ def test_long_read_three_tiles(bc, P):
     same(bc.insertions(0, 1, 0), t, off)
 
 
+def test_int32_edge(bc, P):
+    """Anchors at 2^31 - 2, 2^31 - 1, 2^31, on both sides of a tile edge below
+    2^31 and below 2^32 behind a skip of 1.9 * 10^9 positions
+    (bases_model.int32_edge_case): the table, its filters and the consensus
+    with insertions, with the segments in two orders, the reads in one batch
+    and in two."""
+    H = 1 << 31
+    reads, segs, scrambled, k = bm.int32_edge_case(P)
+    b = bm.make_batch(reads)
+    parts = [bm.slice_batch(b, 0, k), bm.slice_batch(b, k, bm.n_reads(b))]
+    for sg in (segs, scrambled):
+        tids, starts, ends = segments(sg)
+        t = im.table_model(b, tids, starts, ends)
+        off = count(bc, sg, b)
+        one = bc.insertions(0, 1, 0)
+        same(one, t, off)
+        a, far = sg.index(segs[0]), sg.index(segs[1])
+        for p in (H - 2, H - 1, H, segs[0][1] + P - 1, segs[0][1] + P):
+            assert int(off[a]) + p - segs[0][1] in one.index.tolist(), p
+        assert ((one.index >= off[far]) & (one.index < off[far + 1])).sum() == 1
+        _, planes = bm.counts_model(b, tids, starts, ends)
+        assert np.array_equal(bc.counts(), planes)
+        check_table(bc, t, off, planes, [(0, 1, 0), (3, 2, 0), (1, 1, 300000)])
+        got = check_cons(bc, planes, off, t)
+        assert got.inserted[a, 0] >= 7 and got.inserted[far, 0] == 1
+        check_cons(bc, planes, off, t, min_depth=2, min_count=2, call_ppm=200000, iupac=True)
+        count(bc, sg, parts)
+        assert got_bytes(bc.insertions(0, 1, 0)) == got_bytes(one)
+        assert np.array_equal(bc.counts(), planes)
+
+
 # --------------------------------------------------------------- sort sizes
 
 def anchor_table(pos_index, rows):

@@ -157,6 +157,32 @@ def test_multi_segment(eng, TW):
     assert eng._runs.timing()["tiles"] == k
 
 
+# ------------------------------------------------- segments far past the extent
+
+def test_segments_at_2_31_and_2_40(eng, TW):
+    """Segments around 2^31 and ending at 2^40 (the largest end the call
+    accepts), about 3 T positions each, beside one inside the extent: one
+    zero run per far segment, its start reported exactly in 64 bits."""
+    T, _ = TW
+    rng = np.random.default_rng(17)
+    L = T + 9
+    v = rng.integers(0, 3, size=L)
+    v[0] = v[-1] = 1
+    o = load_vectors(eng, [np.array([1, 2, 1]), v])
+    far = [(1, 2 ** 31 - 5, 2 ** 31 + T + 5), (1, 2 ** 40 - 3 * T - 7, 2 ** 40), (0, 2 ** 31 - 5, 2 ** 31 + T + 5),
+           (1, 2 ** 31 - 1, 2 ** 31), (1, 2 ** 31, 2 ** 31 + 1), (1, 2 ** 40 - 1, 2 ** 40)]
+    segs = far[:2] + [(1, 5, L + 3)] + far[2:]
+    tids, starts, ends = (np.array(x, np.int64) for x in zip(*segs))
+    assert ends.max() == 2 ** 40 and (ends - starts).max() <= 3 * T + 7
+    for edges, zero in ((None, 0), ([0, 2], 1), ([1, 2], 0)):
+        got = check(eng, o, tids, starts, ends, edges)
+        for i in (0, 1, 3, 4, 5, 6):
+            s, e, val = got.segment(i)
+            assert s.tolist() == [int(starts[i])] and e.tolist() == [int(ends[i])] and val.tolist() == [zero]
+        assert got.seg_first[3] - got.seg_first[2] > 2 and got.segment(2)[1][-1] == L + 3
+    assert got.start.max() == 2 ** 40 - 1 and got.ends().max() == 2 ** 40
+
+
 # ---------------------------------------------------------------- quantisation
 
 @pytest.mark.parametrize("edges", [[1], [1, 4, 100], list(range(1, 17)), [3, 2 ** 31 - 1]])

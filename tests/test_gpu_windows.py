@@ -214,6 +214,38 @@ def test_many_segments(eng, DIMS):
     check_hist(eng, o, tids, starts, ends, 5)
 
 
+# ------------------------------------------------- segments far past the extent
+
+def test_segments_at_2_31_and_2_40(eng, DIMS):
+    """Segments around 2^31 and ending at 2^40 (the largest end the calls
+    accept), about 3 T positions each, beside one inside the extent: sums,
+    threshold counts and histogram all zero there, the window bounds exact
+    in 64 bits, for windows that do not divide the segments."""
+    T = DIMS[0]
+    rng = np.random.default_rng(17)
+    L = T + 9
+    v = rng.integers(1, 4, size=L)
+    o = load_vectors(eng, [np.array([1, 2, 1]), v])
+    far = [(1, 2 ** 31 - 5, 2 ** 31 + T + 5), (1, 2 ** 40 - 3 * T - 7, 2 ** 40), (0, 2 ** 31 - 5, 2 ** 31 + T + 5),
+           (1, 2 ** 31 - 1, 2 ** 31), (1, 2 ** 31, 2 ** 31 + 1), (1, 2 ** 40 - 1, 2 ** 40)]
+    segs = far[:2] + [(1, 5, L + 3)] + far[2:]
+    tids, starts, ends = (np.array(x, np.int64) for x in zip(*segs))
+    assert ends.max() == 2 ** 40 and (ends - starts).max() <= 3 * T + 7
+    is_far = np.array([s != segs[2] for s in segs])
+    for window in (0, 16, 100, 1000, T + 5):
+        assert window == 0 or any((int(b) - int(a)) % window for _, a, b in far[:3])
+        got = check(eng, o, tids, starts, ends, window, [0, 1, 3])
+        seg, ws, we = windows_model.window_bounds(starts, ends, window)
+        assert np.array_equal(got.segment_of(), seg)
+        assert np.array_equal(got.start(), ws) and np.array_equal(got.end(), we)
+        f = is_far[seg]
+        assert not got.sum[f].any() and not got.ge[f, 1:].any() and got.sum[~f].sum() == v[5:].sum()
+        assert np.array_equal(got.ge[:, 0], we - ws)
+        assert got.start().max() == 2 ** 40 - 1 and got.end().max() == 2 ** 40
+    h = check_hist(eng, o, tids, starts, ends, 4)
+    assert np.array_equal(h[is_far, 0], (ends - starts)[is_far]) and not h[is_far, 1:].any()
+
+
 # ------------------------------------------------------------------ thresholds
 
 @pytest.mark.parametrize("thr", [[], [3], list(range(1, 17)), [0, 4, 100, 101, 2 ** 31 - 1]])

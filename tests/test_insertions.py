@@ -38,6 +38,32 @@ def test_model_matches_loop(seed):
     assert keys == sorted(set(keys))                                   # sorted and unique
 
 
+def test_model_at_the_int32_edge(lib_built):
+    """bases_model.int32_edge_case (the GPU tests' read set): the table model
+    against the literal walk, with anchors at 2^31 - 2, 2^31 - 1, 2^31, on
+    both sides of a tile edge and below 2^32; the consensus with them."""
+    from metacov_amd import bases as mb
+    P = mb.dims()
+    H = 1 << 31
+    reads, segs, scrambled, k = bm.int32_edge_case(P)
+    b = bm.make_batch(reads)
+    for sg in (segs, scrambled):
+        tids, starts, ends = (np.array(x, np.int64) for x in zip(*sg))
+        got, want = im.table_model(b, tids, starts, ends), im.table_loop(b, tids, starts, ends)
+        assert im.table_rows(got) == im.table_rows(want) and (got["count"] > 1).any()
+        two = im.table_model([bm.slice_batch(b, 0, k), bm.slice_batch(b, k, bm.n_reads(b))], tids, starts, ends)
+        assert im.table_rows(two) == im.table_rows(got)
+        off, planes = bm.counts_model(b, tids, starts, ends)
+        a, far, one = sg.index(segs[0]), sg.index(segs[1]), sg.index(segs[2])
+        have = set(got["i"].tolist())
+        for p in (H - 2, H - 1, H, segs[0][1] + P - 1, segs[0][1] + P, segs[0][1] + 2 * P - 1, segs[0][1] + 2 * P):
+            assert int(off[a]) + p - segs[0][1] in have, p
+        assert int(off[one]) in have                                       # 2^31 - 1 again, in its own segment
+        assert any(off[far] <= i < off[far + 1] for i in have)            # the skip reads' insertion
+        first, summary, inserted, aligned, compact = im.consensus_model(planes, off, got)
+        assert inserted[a, 0] >= 7 and inserted[far, 0] == 1 and inserted[one, 0] == 1
+
+
 # ------------------------------------------------------------- hand cases
 
 SEG, HAND = im.SEG, im.HAND

@@ -43,6 +43,25 @@ def test_model_matches_loop(seed):
         assert x.dtype == y.dtype and np.array_equal(x, y)
 
 
+def test_model_far_past_the_extent():
+    """Segments around 2^31 and ending at 2^40 (the GPU test's): the model
+    against the loop, one zero run each with its start exact."""
+    rng = np.random.default_rng(3)
+    depth, ext, coff, _, _, _ = _random_case(rng)
+    segs = [(0, 2 ** 31 - 5, 2 ** 31 + 70), (0, 2 ** 40 - 200, 2 ** 40), (0, 0, int(ext[0]) + 3), (0, 2 ** 31 - 1, 2 ** 31),
+            (0, 2 ** 40 - 1, 2 ** 40)]
+    tids, starts, ends = (np.array(x, np.int64) for x in zip(*segs))
+    for edges in (None, [0, 2], [1]):
+        a = runs_model.runs_model(depth, ext, coff, tids, starts, ends, edges)
+        b = runs_model.runs_loop(depth, ext, coff, tids, starts, ends, edges)
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and np.array_equal(x, y)
+        sf, start, value = a
+        for i in (0, 1, 3, 4):
+            assert start[sf[i]:sf[i + 1]].tolist() == [segs[i][1]]
+            assert value[sf[i]:sf[i + 1]].tolist() == [1 if edges == [0, 2] else 0]
+
+
 def test_model_by_hand():
     depth = np.array([0, 0, 2, 2, 5, 0, 7, 7], np.int32)      # contig 0: [0,5) ; contig 1: [5,8)
     ext, coff = np.array([5, 3]), np.array([0, 5])

@@ -49,6 +49,27 @@ def test_model_matches_loop(seed):
         assert np.array_equal(h.sum(axis=1), ends - starts)
 
 
+def test_model_far_past_the_extent():
+    """Segments around 2^31 and ending at 2^40 (the GPU test's): the models
+    against the loops, zero sums there, the window bounds exact."""
+    rng = np.random.default_rng(3)
+    depth, ext, coff, _, _, _ = _random_case(rng)
+    segs = [(0, 2 ** 31 - 5, 2 ** 31 + 70), (0, 2 ** 40 - 200, 2 ** 40), (0, 0, int(ext[0]) + 3), (0, 2 ** 31 - 1, 2 ** 31),
+            (0, 2 ** 40 - 1, 2 ** 40)]
+    tids, starts, ends = (np.array(x, np.int64) for x in zip(*segs))
+    for window in (0, 16, 17, 1000):
+        a = windows_model.windows_model(depth, ext, coff, tids, starts, ends, window, [0, 1])
+        b = windows_model.windows_loop(depth, ext, coff, tids, starts, ends, window, [0, 1])
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y)
+        seg, ws, we = windows_model.window_bounds(starts, ends, window)
+        assert np.array_equal(a[2][:, 0], we - ws) and not a[1][seg != 2].any() and not a[2][seg != 2, 1].any()
+        assert ws.max() == 2 ** 40 - 1 and we.max() == 2 ** 40 and len(ws) == len(a[1])
+    h = windows_model.hist_model(depth, ext, coff, tids, starts, ends, 4)
+    assert np.array_equal(h, windows_model.hist_loop(depth, ext, coff, tids, starts, ends, 4))
+    assert np.array_equal(h[[0, 1, 3, 4], 0], (ends - starts)[[0, 1, 3, 4]])
+
+
 def test_model_by_hand():
     depth = np.array([0, 0, 2, 2, 5, 0, 7, 7], np.int32)      # contig 0: [0,5) ; contig 1: [5,8)
     ext, coff = np.array([5, 3]), np.array([0, 5])
