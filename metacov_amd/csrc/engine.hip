@@ -1739,7 +1739,10 @@ static int depth_stats_once(mc_ctx* ctx, int64_t R, const int32_t* tid, const in
         const int64_t ext = ctx->extent[t];
         const double body = ext > 2 * span_mean ? (double)ext - span_mean : (double)ext;
         const double depth_est = ext > 0 ? (double)ctx->cbases[t] / body : 0.0;
-        return (int32_t)std::max<int64_t>(0, std::llround(depth_est) - win_below);
+        // (llrint, halves to even: what window_bases_kernel and
+        // direct_window_base compute, so that a batch gets the same windows
+        // whichever of them places them)
+        return (int32_t)std::max<int64_t>(0, std::llrint(depth_est) - win_below);
     };
     const bool same = R > 0 && fc.valid && (int64_t)fc.tid.size() == R &&
                       std::memcmp(fc.tid.data(), tid, R * 4) == 0 &&

@@ -871,8 +871,9 @@ probe_kernel(ProbeArgs A) {
 // The full prepare's window bases on the device (a repeated call over the
 // same layout with a new batch): the estimate the host makes at staging time
 // (depth over the contig less one mean read span, kWinBelow bins of the
-// window below it) from ingest's per-contig bases, with the contig length
-// for the extent.  One thread per region row.
+// window below it) from ingest's per-contig bases and extents (the contig
+// length, or the furthest read end past it), bit for bit the host's
+// window_base.  One thread per region row.
 __global__ void __launch_bounds__(kBlock)
 window_bases_kernel(const unsigned long long* __restrict__ ingest_out, const unsigned long long* __restrict__ cbases,
                     int64_t n, const int64_t* __restrict__ len, const int32_t* __restrict__ rtid,
@@ -882,7 +883,8 @@ window_bases_kernel(const unsigned long long* __restrict__ ingest_out, const uns
     if (r >= R) return;
     const int t = rtid[r];
     const double mean = n > 0 ? (double)ingest_out[2] / (double)n : 0.0;
-    const double ext = (double)len[t];
+    const long long max_end = (long long)ingest_out[8 + t];   // ingest's furthest read end of contig t
+    const double ext = (double)(max_end > len[t] ? max_end : (long long)len[t]);
     const double body = ext > 2.0 * mean ? ext - mean : ext;
     const double est = ext > 0 ? (double)cbases[t] / body : 0.0;
     const long long b0 = llrint(est) - win_below;
