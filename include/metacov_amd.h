@@ -449,7 +449,53 @@ int mc_windows_dims(int32_t* tile, int32_t* min_window, int32_t* max_bins, int32
  * (mc_bases_src_counts).  An unsorted file is MC_E_INVALID.  mc_bases_src_next
  * hands out up to max_reads reads (it stops once max_bases bases are in);
  * *n == 0 at the end of the file.  mc_bases_src_batch: the arrays of the last
- * batch, valid until the next call on the source. */
+ * batch, valid until the next call on the source.
+ *
+ * Strand (opt-in, as the insertion alleles are).  A read is on the reverse
+ * strand iff flag & 0x10; no other flag bit matters.  Every count a read makes
+ * (A, C, G, T, N, DEL) belongs to its strand; a deletion takes the strand of
+ * the read it is in.  mc_bases_track_strand(h, on): on = 1 / 0 makes the NEXT
+ * mc_bases_begin also allocate and zero rev[6][N] (or not); another value is
+ * MC_E_INVALID.  rev is indexed exactly like the planes and holds the counts
+ * of the reverse-strand reads; the six planes stay the totals, so
+ * mc_bases_get, _sites, _consensus and _insertions give the same results with
+ * tracking on as off, and forward = total - rev.  Integer only, exact,
+ * independent of the batch split, repeatable.
+ *   Reads: mc_bases_add_batch_flags / _add_batch_device_flags take the nine
+ * arrays plus flag[n] (uint16, the BAM flag words; a device pointer for the
+ * device call; a sub-range of a resident table is d_flag + a); checks and
+ * error messages are mc_bases_add_batch's.  On a handle that tracks strand the
+ * flag-less calls are MC_E_STATE (the message says the flags are needed); on
+ * one that does not, the new calls ignore the flags and are the old ones.
+ *   Fetch: mc_bases_get_reverse copies positions [first, first + count) of the
+ * reverse planes to out[6][count]; mc_bases_reverse_device exposes them (plane
+ * c at d_rev + c * stride).  mc_bases_set_strand (test hook): sets both plane
+ * sets from total[6][count] and rev[6][count]; rev > total anywhere is
+ * MC_E_INVALID (checked on the host, nothing is written); sites and consensus
+ * results are gone as after mc_bases_set.  (mc_bases_set itself leaves the
+ * reverse planes alone.)  All three are MC_E_STATE without tracking.
+ *   Sites: mc_bases_sites_strand.  Alleles are A, C, G, T, DEL; depth and the
+ * base allele are exactly mc_bases_sites'.  Position p is a site iff
+ * depth >= min_depth and some allele i != base has a[i] >= min_count,
+ * a[i] * 10^6 >= min_ppm * depth, fwd[i] >= min_alt_strand and
+ * rev[i] >= min_alt_strand.  With min_alt_strand == 0 that is mc_bases_sites'
+ * predicate and the site list is identical.  A negative min_alt_strand is
+ * MC_E_INVALID, a handle without tracking MC_E_STATE.  The result lands in
+ * mc_bases_sites' buffers (mc_bases_sites_first and _sites_get read it);
+ * mc_bases_sites_get_reverse copies the sites' reverse counts
+ * rev_counts[count][6] (MC_E_STATE after a plain mc_bases_sites).
+ *   Device side: a second instantiation of the pileup kernel, same 48 KiB of
+ * LDS, no global atomics, one owner per tile.  A tile that looks at no more
+ * than 65535 reads counts forward in the low and reverse in the high 16 bits
+ * of each LDS word (a read covers a position at most once, so neither half
+ * can carry) and its flush adds low + high to the total plane and high to the
+ * reverse plane; a tile with more reads walks them twice with 32-bit words,
+ * the forward reads, a flush, then the reverse reads.
+ *   Sources: mc_bases_src_flags gives the flags of the last batch (valid as
+ * long as mc_bases_src_batch's arrays); the GPU decoder's bases mode always
+ * fills a flag column (mc_bam_gpu_bases_flags, _bases_copy_flags).
+ *   Not covered: the strand of insertion alleles, strand in the consensus
+ * rule, strand-bias statistics (floating point: host work over these counts). */
 #define MC_BASES_A   0
 #define MC_BASES_C   1
 #define MC_BASES_G   2
@@ -492,6 +538,24 @@ int mc_bases_sites_get(const mc_bases* h, int64_t first, int64_t count, int64_t*
 int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pileup_ms, float* sites_ms, int64_t* tiles,
                     int64_t* reads);
 int mc_bases_dims(int32_t* tile);
+int mc_bases_track_strand(mc_bases* h, int on);
+int mc_bases_add_batch_flags(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                             const int64_t* cig_off /* n + 1 */, const uint32_t* cigar, const int32_t* l_seq,
+                             const int64_t* seq_off /* n + 1 */, const uint8_t* seq,
+                             const int64_t* qual_off /* n + 1 */, const uint8_t* qual, const uint16_t* flag /* n */);
+int mc_bases_add_batch_device_flags(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                                    const int64_t* d_cig_off /* n + 1 */, const uint32_t* d_cigar, int64_t n_words,
+                                    const int32_t* d_l_seq, const int64_t* d_seq_off /* n + 1 */,
+                                    const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off /* n + 1 */,
+                                    const uint8_t* d_qual, int64_t qual_bytes, const uint16_t* d_flag /* n */);
+int mc_bases_get_reverse(const mc_bases* h, int64_t first, int64_t count, uint32_t* out /* 6 x count */);
+int mc_bases_reverse_device(const mc_bases* h, const uint32_t** d_rev, int64_t* stride, int64_t* n);
+int mc_bases_set_strand(mc_bases* h, int64_t first, int64_t count, const uint32_t* total /* 6 x count */,
+                        const uint32_t* rev /* 6 x count */);
+int mc_bases_sites_strand(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                          int64_t min_alt_strand, const uint8_t* ref /* N, or NULL */, int64_t* n_sites);
+int mc_bases_sites_get_reverse(const mc_bases* h, int64_t first, int64_t count,
+                               uint32_t* rev_counts /* count x 6 */);
 
 /* Consensus (mc_bases_consensus), a third stage over the planes on the device:
  * one letter per position, called from the counts alone.  Without
@@ -654,6 +718,7 @@ int mc_bases_src_next(mc_bases_src* s, int64_t max_reads, int64_t max_bases, int
 int mc_bases_src_batch(const mc_bases_src* s, const int32_t** tid, const int32_t** pos, const int64_t** cig_off,
                        const uint32_t** cigar, const int32_t** l_seq, const int64_t** seq_off,
                        const uint8_t** seq, const int64_t** qual_off, const uint8_t** qual);
+int mc_bases_src_flags(const mc_bases_src* s, const uint16_t** flag /* n of the last batch */);
 int mc_bases_src_counts(const mc_bases_src* s, int64_t* records, int64_t* kept, int64_t* no_seq,
                         int64_t* bad_cigar);
 
@@ -879,6 +944,11 @@ int mc_bam_gpu_bases_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_t
 int mc_bam_gpu_bases_copy(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int64_t* cig_off /* n + 1 */,
                           uint32_t* cigar, int32_t* l_seq, int64_t* seq_off /* n + 1 */, uint8_t* seq,
                           int64_t* qual_off /* n + 1 */, uint8_t* qual);
+/* The flag column of the bases-mode read table (2 bytes per read, written by
+ * the fill walk beside tid / pos / l_seq): the device pointer (a sub-range
+ * [a, a + n) is *d_flag + a), or a copy to flag[n] on the host. */
+int mc_bam_gpu_bases_flags(const mc_bam_gpu* g, const uint16_t** d_flag);
+int mc_bam_gpu_bases_copy_flags(const mc_bam_gpu* g, uint16_t* flag /* n */);
 int mc_bam_gpu_bases_counts(const mc_bam_gpu* g, int64_t* records, int64_t* kept, int64_t* no_seq,
                             int64_t* bad_cigar);
 /* The same for one rank's contigs (mc_bam_gpu_open_extents' blocks and

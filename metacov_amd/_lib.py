@@ -160,6 +160,16 @@ SIGNATURES = {
     "mc_bases_consensus_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                   ctypes.POINTER(ctypes.c_float)],
     "mc_bases_set": [_P, _I64, _I64, _P],
+    # strand (opt-in): the reverse-strand reads' planes beside the totals
+    "mc_bases_track_strand": [_P, ctypes.c_int],
+    "mc_bases_add_batch_flags": [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mc_bases_add_batch_device_flags": [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P],
+    "mc_bases_get_reverse": [_P, _I64, _I64, _P],
+    "mc_bases_reverse_device": [_P, _PP, _PI64, _PI64],
+    "mc_bases_set_strand": [_P, _I64, _I64, _P, _P],
+    "mc_bases_sites_strand": [_P, _I64, _I64, _I64, _I64, _P, _PI64],
+    "mc_bases_sites_get_reverse": [_P, _I64, _I64, _P],
+    "mc_bases_src_flags": [_P, _PP],
     # insertion alleles (csrc/bases_ins.h)
     "mc_bases_track_insertions": [_P, ctypes.c_int],
     "mc_bases_insertions": [_P, _I64, _I64, _I64, _PI64],
@@ -216,6 +226,8 @@ SIGNATURES = {
     "mc_bam_gpu_bases_device": [_P, _PI64, _PP, _PP, _PP, _PP, _PI64, _PP, _PP, _PP, _PI64, _PP, _PP, _PI64],
     "mc_bam_gpu_bases_copy": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "mc_bam_gpu_bases_counts": [_P, _PI64, _PI64, _PI64, _PI64],
+    "mc_bam_gpu_bases_flags": [_P, _PP],
+    "mc_bam_gpu_bases_copy_flags": [_P, _P],
     "mc_bam_index_extents": [ctypes.c_char_p, _I32, _P, _PI64],
     "mc_bam_gpu_open_contigs": [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _U32, _I32, _P,
                                 _PP],

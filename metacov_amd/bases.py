@@ -22,7 +22,11 @@ counterpart.  The contract (CIGAR walk, channels, quality rule, segments,
 sites, the consensus rule, insertion alleles) is the header's.  Insertions
 are opt-in: begin(..., insertions=True) collects the I ops' alleles beside the
 planes, insertions() returns their grouped table and consensus(...,
-insertions=True) writes the called ones into the compact letters.
+insertions=True) writes the called ones into the compact letters.  Strand is
+opt-in too: begin(..., strand=True) keeps the counts of the reverse-strand
+reads (flag & 0x10) beside the totals (counts_reverse(); forward = counts() -
+counts_reverse()), and sites(..., min_alt_strand=K) asks for an alternative
+allele seen K times on each strand.
 """
 import ctypes
 
@@ -56,12 +60,15 @@ def ins_dims(lib=None):
 class Sites:
     """Sites of S segments, in segment order: segment s owns rows
     first[s] .. first[s + 1]; pos [n] int64 relative to the contig, ascending
-    within a segment; counts [n, 6] uint32 (A, C, G, T, N, DEL)."""
+    within a segment; counts [n, 6] uint32 (A, C, G, T, N, DEL); rev_counts
+    [n, 6] uint32, the reverse-strand reads' share of counts, on a counter
+    that tracks strand, else None."""
 
-    def __init__(self, first, pos, counts):
+    def __init__(self, first, pos, counts, rev_counts=None):
         self.first = np.asarray(first, np.int64)
         self.pos = np.asarray(pos, np.int64)
         self.counts = np.asarray(counts, np.uint32).reshape(-1, 6)
+        self.rev_counts = None if rev_counts is None else np.asarray(rev_counts, np.uint32).reshape(-1, 6)
 
     def __len__(self):
         return len(self.pos)
@@ -156,6 +163,7 @@ class BaseSource:
         n = ctypes.c_int64()
         check(self._lib.mc_bases_src_next(self._h, int(max_reads), int(max_bases), ctypes.byref(n)), self._lib)
         n = n.value
+        self._n = n
         if n == 0:
             return None
         p = [ctypes.c_void_p() for _ in range(9)]
@@ -174,6 +182,17 @@ class BaseSource:
                 "cigar": view(p[3], np.uint32, int(cig_off[n])), "l_seq": view(p[4], np.int32, n),
                 "seq_off": seq_off, "seq": view(p[6], np.uint8, int(seq_off[n])),
                 "qual_off": qual_off, "qual": view(p[8], np.uint8, int(qual_off[n]))}
+
+    def flags(self):
+        """uint16 [n]: the BAM flag words of the last batch next() returned (a
+        view, valid until the next call); the strand is flag & 0x10."""
+        n = getattr(self, "_n", 0)
+        if n == 0:
+            return np.zeros(0, np.uint16)
+        p = ctypes.c_void_p()
+        check(self._lib.mc_bases_src_flags(self._h, ctypes.byref(p)), self._lib)
+        buf = (ctypes.c_char * (2 * n)).from_address(p.value)
+        return np.frombuffer(buf, dtype=np.uint16, count=n)
 
     def counts(self):
         """Records read so far: total, kept (past the filters), and the kept
@@ -228,6 +247,10 @@ class GpuBaseSource:
         self.n = n.value
         self.n_words, self.seq_bytes, self.qual_bytes = nw.value, sb.value, qb.value
         self._dptr = [x.value or 0 for x in p]   # tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual
+        f = ctypes.c_void_p()
+        if hasattr(self._lib, "mc_bam_gpu_bases_flags"):             # (an A/B build of an older revision has none)
+            check(self._lib.mc_bam_gpu_bases_flags(self._h, r(f)), self._lib)
+        self._dflag = f.value or 0               # the flag column, uint16 per read
         self._lib.mc_bam_gpu_trim(self._h, None)  # the decode's staging is not needed again
 
     def __len__(self):
@@ -257,6 +280,12 @@ class GpuBaseSource:
               self._lib)
         return out
 
+    def copy_flags(self):
+        """uint16 [n]: the reads' BAM flag words on the host."""
+        out = np.zeros(self.n, np.uint16)
+        check(self._lib.mc_bam_gpu_bases_copy_flags(self._h, ptr(out)), self._lib)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.mc_bam_gpu_close(self._h)
@@ -284,6 +313,7 @@ class BaseCounter:
         self.n_ref = int(n_ref)
         self.device = int(device)
         self._S = 0
+        self.strand = False
         check(self._lib.mc_bases_create(self.device, self.n_ref, ctypes.byref(self._h)), self._lib)
 
     def close(self):
@@ -303,23 +333,33 @@ class BaseCounter:
     def __exit__(self, *exc):
         self.close()
 
-    def begin(self, tids, starts, ends, min_baseq=0, insertions=False):
+    def begin(self, tids, starts, ends, min_baseq=0, insertions=False, strand=False):
         """Allocates and zeroes the planes of the segments [start, end) of
         contig tid; returns N, the positions in all.  insertions: also collect
-        the reads' insertion alleles (insertions(), consensus(insertions=True))."""
+        the reads' insertion alleles (insertions(), consensus(insertions=True)).
+        strand: also keep the reverse-strand reads' counts (counts_reverse(),
+        sites(min_alt_strand=...)); the reads then come with their flags."""
         tids = np.ascontiguousarray(tids, dtype=np.int32)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
         ends = np.ascontiguousarray(ends, dtype=np.int64)
         if not len(tids) == len(starts) == len(ends):
             raise ValueError("tids / starts / ends lengths differ")
         check(self._lib.mc_bases_track_insertions(self._h, int(bool(insertions))), self._lib)
+        if strand or hasattr(self._lib, "mc_bases_track_strand"):    # (an A/B build of an older revision has none)
+            check(self._lib.mc_bases_track_strand(self._h, int(bool(strand))), self._lib)
+        self.strand = False
         check(self._lib.mc_bases_begin(self._h, len(tids), ptr(tids), ptr(starts), ptr(ends), int(min_baseq)),
               self._lib)
+        self.strand = bool(strand)
         self._S = len(tids)
         return int(self.seg_off[-1])
 
-    def add_reads(self, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual):
-        """One batch of reads sorted by (tid, pos) (mc_bases_add_batch)."""
+    def add_reads(self, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, flag=None):
+        """One batch of reads sorted by (tid, pos) (mc_bases_add_batch); flag:
+        the reads' BAM flag words, required on a counter that tracks strand
+        (mc_bases_add_batch_flags)."""
+        if self.strand and flag is None:
+            raise ValueError("the counter tracks strand: add_reads needs the reads' flags")
         tid = np.ascontiguousarray(tid, dtype=np.int32)
         n = len(tid)
         pos = np.ascontiguousarray(pos, dtype=np.int32)
@@ -332,6 +372,14 @@ class BaseCounter:
             raise ValueError("read arrays of inconsistent length")
         if n and (cig_off[n] > len(cigar) or seq_off[n] > len(seq) or qual_off[n] > len(qual)):
             raise ValueError("the last offset exceeds its arena")
+        if flag is not None:
+            flag = np.ascontiguousarray(flag, dtype=np.uint16)
+            if len(flag) != n:
+                raise ValueError("read arrays of inconsistent length")
+            check(self._lib.mc_bases_add_batch_flags(self._h, n, ptr(tid), ptr(pos), ptr(cig_off), ptr(cigar),
+                                                     ptr(l_seq), ptr(seq_off), ptr(seq), ptr(qual_off), ptr(qual),
+                                                     ptr(flag)), self._lib)
+            return
         check(self._lib.mc_bases_add_batch(self._h, n, ptr(tid), ptr(pos), ptr(cig_off), ptr(cigar), ptr(l_seq),
                                            ptr(seq_off), ptr(seq), ptr(qual_off), ptr(qual)), self._lib)
 
@@ -351,6 +399,12 @@ class BaseCounter:
 
         for a in range(0, src.n, int(max_reads)):
             n = min(int(max_reads), src.n - a)
+            if self.strand:
+                check(self._lib.mc_bases_add_batch_device_flags(
+                    self._h, n, at(tid, a, 4), at(pos, a, 4), at(cig_off, a, 8), at(cigar, 0, 4), src.n_words,
+                    at(l_seq, a, 4), at(seq_off, a, 8), at(seq, 0, 1), src.seq_bytes, at(qual_off, a, 8),
+                    at(qual, 0, 1), src.qual_bytes, at(src._dflag, a, 2)), self._lib)
+                continue
             check(self._lib.mc_bases_add_batch_device(
                 self._h, n, at(tid, a, 4), at(pos, a, 4), at(cig_off, a, 8), at(cigar, 0, 4), src.n_words,
                 at(l_seq, a, 4), at(seq_off, a, 8), at(seq, 0, 1), src.seq_bytes, at(qual_off, a, 8),
@@ -377,7 +431,7 @@ class BaseCounter:
                 if b is None:
                     break
                 self.add_reads(b["tid"], b["pos"], b["cig_off"], b["cigar"], b["l_seq"], b["seq_off"], b["seq"],
-                               b["qual_off"], b["qual"])
+                               b["qual_off"], b["qual"], flag=src.flags() if self.strand else None)
             return src.counts()
 
     @property
@@ -396,23 +450,46 @@ class BaseCounter:
         check(self._lib.mc_bases_get(self._h, int(first), int(count), ptr(out)), self._lib)
         return out
 
-    def sites(self, min_depth=1, min_count=1, min_ppm=0, ref=None):
+    def counts_reverse(self, first=0, count=None):
+        """uint32 [6, count]: the reverse-strand reads' share of counts() over
+        the same plane indices; needs begin(..., strand=True)."""
+        if count is None:
+            count = int(self.seg_off[-1]) - int(first)
+        out = np.zeros((6, max(int(count), 0)), np.uint32)
+        check(self._lib.mc_bases_get_reverse(self._h, int(first), int(count), ptr(out)), self._lib)
+        return out
+
+    def sites(self, min_depth=1, min_count=1, min_ppm=0, ref=None, min_alt_strand=0):
         """The sites among the positions (see the header); ref: optional uint8
-        [N], indexed like a plane, 0..3 = A/C/G/T, anything else unknown."""
+        [N], indexed like a plane, 0..3 = A/C/G/T, anything else unknown.
+        min_alt_strand (needs begin(..., strand=True)): a site needs one
+        alternative allele that passes min_count and min_ppm and is seen this
+        many times on each strand.  On a counter that tracks strand the
+        result carries rev_counts."""
+        if min_alt_strand and not self.strand:
+            raise ValueError("min_alt_strand needs a counter that tracks strand (begin(..., strand=True))")
         if ref is not None:
             ref = np.ascontiguousarray(ref, dtype=np.uint8)
             if len(ref) != int(self.seg_off[-1]):
                 raise ValueError("the reference plane must have one entry per position")
         n = ctypes.c_int64()
-        check(self._lib.mc_bases_sites(self._h, int(min_depth), int(min_count), int(min_ppm), ptr(ref),
-                                       ctypes.byref(n)), self._lib)
+        if self.strand:
+            check(self._lib.mc_bases_sites_strand(self._h, int(min_depth), int(min_count), int(min_ppm),
+                                                  int(min_alt_strand), ptr(ref), ctypes.byref(n)), self._lib)
+        else:
+            check(self._lib.mc_bases_sites(self._h, int(min_depth), int(min_count), int(min_ppm), ptr(ref),
+                                           ctypes.byref(n)), self._lib)
         n = n.value
         first = np.zeros(self._S + 1, np.int64)
         check(self._lib.mc_bases_sites_first(self._h, ptr(first)), self._lib)
         pos = np.zeros(n, np.int64)
         cnt = np.zeros((n, 6), np.uint32)
         check(self._lib.mc_bases_sites_get(self._h, 0, n, ptr(pos), ptr(cnt)), self._lib)
-        return Sites(first, pos, cnt)
+        rev = None
+        if self.strand:
+            rev = np.zeros((n, 6), np.uint32)
+            check(self._lib.mc_bases_sites_get_reverse(self._h, 0, n, ptr(rev)), self._lib)
+        return Sites(first, pos, cnt, rev)
 
     def insertions(self, min_depth=1, min_count=1, min_ppm=0):
         """The grouped insertion alleles (see the header, "Insertion alleles")
@@ -450,13 +527,21 @@ class BaseCounter:
                                                    ctypes.byref(n)), self._lib)
         return {"extract_ms": a.value, "group_ms": b.value, "consensus_ms": c.value, "events": n.value}
 
-    def set_counts(self, first, planes):
+    def set_counts(self, first, planes, rev=None):
         """Test hook (mc_bases_set): overwrites plane indices first .. first +
         count with planes, uint32 [6, count]; sites and consensus results are
-        gone afterwards."""
+        gone afterwards.  rev (mc_bases_set_strand, needs strand=True): the
+        reverse planes of the same range, rev <= planes everywhere."""
         planes = np.ascontiguousarray(planes, dtype=np.uint32)
         if planes.ndim != 2 or planes.shape[0] != 6:
             raise ValueError("planes must be [6, count]")
+        if rev is not None:
+            rev = np.ascontiguousarray(rev, dtype=np.uint32)
+            if rev.shape != planes.shape:
+                raise ValueError("rev must have the shape of planes")
+            check(self._lib.mc_bases_set_strand(self._h, int(first), planes.shape[1], ptr(planes), ptr(rev)),
+                  self._lib)
+            return
         check(self._lib.mc_bases_set(self._h, int(first), planes.shape[1], ptr(planes)), self._lib)
 
     def consensus(self, min_depth=1, min_count=1, call_ppm=0, iupac=False, fill_ref=False, ref=None,
@@ -541,6 +626,8 @@ def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, mi
 # ------------------------------------------------------------------ output
 
 HEADER = "contig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tDEL\n"
+HEADER_STRAND = (HEADER[:-1] + "".join("\t%s_fwd" % c for c in CHANNELS) +
+                 "".join("\t%s_rev" % c for c in CHANNELS) + "\n")
 _REF_CODE = np.full(256, 4, np.uint8)
 for _i, _ch in enumerate("ACGT"):
     _REF_CODE[ord(_ch)] = _REF_CODE[ord(_ch.lower())] = _i
@@ -551,11 +638,13 @@ def ref_codes(letters):
     return _REF_CODE[np.asarray(letters, np.uint8)]
 
 
-def write_sites(fh, name, pos, counts, ref=None):
+def write_sites(fh, name, pos, counts, ref=None, rev=None):
     """Tab-separated `contig pos ref depth A C G T N DEL` lines of one contig:
     pos [n] 0-based positions (written 1-based, as mpileup and VCF), counts
     [n, 6], ref [n] uint8 ASCII letters or None ('.').  depth = A + C + G + T
-    + DEL.  Returns the lines written."""
+    + DEL.  rev [n, 6] (the reverse-strand share of counts): twelve more
+    columns, the six forward counts (counts - rev) and the six reverse ones
+    (HEADER_STRAND).  Returns the lines written."""
     pos = np.asarray(pos, np.int64)
     n = len(pos)
     if n == 0:
@@ -568,7 +657,11 @@ def write_sites(fh, name, pos, counts, ref=None):
         letters = np.char.upper(np.asarray(ref, np.uint8).view("S1").astype("U1"))
     line = np.char.add(str(name) + "\t", (pos + 1).astype(str))
     line = np.char.add(np.char.add(line, "\t"), letters)
-    for col in [depth] + [counts[:, c] for c in range(6)]:
+    cols = [depth] + [counts[:, c] for c in range(6)]
+    if rev is not None:
+        rev = np.asarray(rev).reshape(n, 6).astype(np.int64)
+        cols += [counts[:, c] - rev[:, c] for c in range(6)] + [rev[:, c] for c in range(6)]
+    for col in cols:
         line = np.char.add(np.char.add(line, "\t"), col.astype(str))
     fh.write("\n".join(line.tolist()))
     fh.write("\n")

@@ -36,6 +36,7 @@ Base counts (no counterpart in the reference either):
 
     python -m metacov_amd.cli bases -b X.bam [-o out.tsv] [-f ref.fa] [-rc R.csv | -rb R.blast7] [--min-baseq 0]
                                     [--min-mapq 0] [--min-depth 1] [--min-count 1] [--min-frac 0.0] [--all]
+                                    [--strand [--min-alt-strand 0]]
                                     [--decode host|gpu]
 
 writes `contig pos ref depth A C G T N DEL` for the variant sites, or with
@@ -753,18 +754,23 @@ def _segment_letters(fa, name, start, end):
 
 
 def write_bases(path, references, tids, starts, ends, outfile, fasta=None, device=0, min_baseq=0, min_mapq=0,
-                min_depth=1, min_count=1, min_ppm=0, every=False, decode="host", insertions=None):
+                min_depth=1, min_count=1, min_ppm=0, every=False, decode="host", insertions=None, strand=False,
+                min_alt_strand=0):
     """The base-count table of the segments (header contig ids), group by
     group, each written before the next is computed.  decode "host": each
     group is one pass over the BAM on host threads; "gpu": the file is decoded
     once on the device and every group reads the resident records.
     insertions: a text file for the insertion alleles that pass the same
     thresholds with their own count (`contig pos depth count len seq`).
-    Returns (lines written, the source's record counts)."""
+    strand: twelve more columns, the forward and the reverse counts; a site
+    then also needs min_alt_strand reads of an alternative allele on each
+    strand.  Returns (lines written, the source's record counts)."""
     from . import bases as _bases
     import contextlib
     names = [w.split()[0] if w.split() else w for w in references]
-    outfile.write(_bases.HEADER)
+    if min_alt_strand and not strand:
+        raise ValueError("min_alt_strand needs strand")
+    outfile.write(_bases.HEADER_STRAND if strand else _bases.HEADER)
     if insertions is not None:
         insertions.write(_bases.INSERTIONS_HEADER)
     written, counts = 0, None
@@ -783,7 +789,8 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
                                                "run with --decode host (%s)" % (path, device, e))
                 raise
         for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
-            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions is not None)
+            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions is not None,
+                     strand=strand)
             if src is not None:
                 bc.add_device(src)
                 counts = src.counts()
@@ -805,15 +812,18 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
                         planes = bc.counts(o + c0, c1 - c0)
                         written += _bases.write_sites(
                             outfile, names[int(tids[i])], np.arange(starts[i] + c0, starts[i] + c1), planes.T,
-                            None if letters is None else letters[o + c0:o + c1])
+                            None if letters is None else letters[o + c0:o + c1],
+                            rev=bc.counts_reverse(o + c0, c1 - c0).T if strand else None)
             else:
                 s = bc.sites(min_depth, min_count, min_ppm,
-                             ref=None if letters is None else _bases.ref_codes(letters))
+                             ref=None if letters is None else _bases.ref_codes(letters),
+                             min_alt_strand=min_alt_strand)
                 for i in range(a, b):
                     r0, r1 = int(s.first[i - a]), int(s.first[i - a + 1])
                     idx = int(seg_off[i - a]) + (s.pos[r0:r1] - int(starts[i]))
                     written += _bases.write_sites(outfile, names[int(tids[i])], s.pos[r0:r1], s.counts[r0:r1],
-                                                  None if letters is None else letters[idx])
+                                                  None if letters is None else letters[idx],
+                                                  rev=s.rev_counts[r0:r1] if strand else None)
     return written, counts
 
 
@@ -868,12 +878,18 @@ def _write_insertions(bc, names, tids, starts, seg_off, min_depth, min_count, mi
               help="A site needs this fraction (0..1) of its depth on that allele")
 @click.option('--all', 'every', is_flag=True, default=False,
               help="Write every position of the regions, not only the sites")
+@click.option('--strand', is_flag=True, default=False,
+              help="Also write each count per strand: twelve more columns, `A_fwd .. DEL_fwd A_rev .. DEL_rev` "
+                   "(reverse: reads with flag 0x10)")
+@click.option('--min-alt-strand', type=click.IntRange(0), default=0,
+              help="A site needs an allele besides the base allele that passes --min-count and --min-frac and "
+                   "is seen this many times on each strand (needs --strand)")
 @click.option('--device', type=int, default=0, help="HIP device ordinal")
 @click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
               help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
                    "the GPU, the records staying in device memory (the file's reads must fit there)")
 def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regionfile_csv, min_baseq, min_mapq,
-          min_depth, min_count, min_frac, every, device, decode):
+          min_depth, min_count, min_frac, every, strand, min_alt_strand, device, decode):
     """
     Write per-position base counts and variant sites
 
@@ -881,6 +897,8 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     strongest allele besides the base allele (the reference base with -f,
     else the most frequent allele) passes --min-count and --min-frac at a
     depth of at least --min-depth; with --all every position of the regions.
+    --strand adds the counts per strand, --min-alt-strand K keeps the sites
+    whose alternative allele is seen K times on both strands.
     pos is 1-based, as in mpileup and VCF; ref is `.` without -f.  Every
     contig in header order, or the regions of a region file in file order.
     Counted on the GPU; single process only.
@@ -891,6 +909,8 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
         raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
     min_ppm = int(round(min_frac * 1e6))
+    if min_alt_strand and not strand:
+        raise click.UsageError("--min-alt-strand needs --strand")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise click.UsageError("bases runs in one process (WORLD_SIZE > 1 is not supported: "
                                "its output is not sharded)")
@@ -909,7 +929,8 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
         ends = np.asarray(lengths, np.int64)
     n, counts = write_bases(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
                             min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth, min_count=min_count,
-                            min_ppm=min_ppm, every=every, decode=decode, insertions=insertions)
+                            min_ppm=min_ppm, every=every, decode=decode, insertions=insertions, strand=strand,
+                            min_alt_strand=min_alt_strand)
     outfile.flush()
     if insertions is not None:
         insertions.flush()

@@ -37,6 +37,12 @@
 //                         with plain load-add-store: a tile has one owner in
 //                         a launch and the launches of successive batches
 //                         are ordered on the stream.  No global atomics.
+//   bases_pileup_strand_kernel   the same walk on a handle that tracks strand
+//                         (pileup_tile<true>): the reads' flags beside their
+//                         other words, forward and reverse counts in the two
+//                         16-bit halves of the same LDS words (two 32-bit
+//                         walks for a tile with more than 65535 reads), the
+//                         flush into the totals and the reverse planes.
 //   bases_ends_kernel     mc_bases_add_batch_device only (the batch is in
 //                         device memory, e.g. the GPU decoder's bases-mode
 //                         table): one thread writes the first and last read's
@@ -168,94 +174,153 @@ __device__ __forceinline__ int64_t lower_bound(const Batch& b, int32_t tid, int6
     return a;
 }
 
-__global__ __launch_bounds__(kThreads) void bases_pileup_kernel(Batch b, const int32_t* __restrict__ span,
-                                                               const Tile* __restrict__ tiles,
-                                                               const int32_t* __restrict__ order, int32_t max_span,
-                                                               int32_t min_baseq, uint32_t* __restrict__ planes,
-                                                               int64_t stride) {
+// One tile of a batch (the launch comment above).  kStrand: the reads' flags
+// are read too and the counts of the reverse-strand reads (flag & 0x10) also
+// go into the rev planes, in the same 48 KiB of LDS.  A tile that looks at no
+// more than 65535 reads counts both strands in one walk, forward in the low
+// and reverse in the high 16 bits of each LDS word (a read covers a position
+// at most once, so neither half can carry); a tile with more reads walks them
+// twice with full 32-bit words, the forward reads first, then the reverse
+// ones.  Both conditions are uniform over the workgroup.
+template <bool kStrand>
+__device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __restrict__ span,
+                                            const Tile* __restrict__ tiles, const int32_t* __restrict__ order,
+                                            int32_t max_span, int32_t min_baseq, uint32_t* __restrict__ planes,
+                                            int64_t stride, const uint16_t* __restrict__ flag,
+                                            uint32_t* __restrict__ rev) {
     __shared__ __attribute__((aligned(16))) uint32_t acc[kPlanes * kTile];
     const Tile t = tiles[order[blockIdx.x]];
     const int64_t t0 = t.rel, t1 = t.rel + t.n;
     const int64_t lo = lower_bound(b, t.tid, t0 > max_span ? t0 - max_span : 0);
     const int64_t hi = lower_bound(b, t.tid, t1);
     if (lo >= hi) return;
-    for (int k = threadIdx.x * 4; k < kPlanes * kTile; k += kThreads * 4)
-        *reinterpret_cast<uint4*>(&acc[k]) = make_uint4(0, 0, 0, 0);
-    __syncthreads();
+    const bool packed = kStrand && hi - lo <= 65535;
+    const int passes = kStrand && !packed ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    // A wave takes 64 consecutive reads at a time: lane i loads read i's words (coalesced, independent
-    // loads), then the reads that reach the tile are walked one by one with those words broadcast.
-    for (int64_t g = lo + 64 * (int64_t)wave; g < hi; g += 64 * kWaves) {
-        const int64_t mine = g + lane;
-        const bool have = mine < hi;
-        const int32_t m_pos = have ? b.pos[mine] : 0;
-        const int32_t m_span = have ? span[mine] : 0;
-        const int32_t m_l = have ? b.l_seq[mine] : 0;
-        const int64_t m_c0 = have ? b.cig_off[mine] : 0, m_c1 = have ? b.cig_off[mine + 1] : 0;
-        const int64_t m_so = have ? b.seq_off[mine] : 0, m_qo = have ? b.qual_off[mine] : 0;
-        const uint32_t m_cw = m_c1 > m_c0 ? b.cigar[m_c0] : 0u;        // the first op: the only one of most reads
-        const int32_t m_q0 = m_l > 0 ? (int32_t)b.qual[m_qo] : 0;
-        unsigned long long todo = __ballot(have && (int64_t)m_pos + m_span > t0);
-        while (todo) {
-            const int i = __ffsll(todo) - 1;
-            todo &= todo - 1;
-            const int64_t pos = bcast(m_pos, i), l = bcast(m_l, i);
-            const int64_t c0 = bcast64(m_c0, i), c1 = bcast64(m_c1, i);
-            const int64_t so = bcast64(m_so, i), qo = bcast64(m_qo, i);
-            const bool test_q = min_baseq > 0 && !(l > 0 && bcast(m_q0, i) == 0xFF);
-            int64_t rp = pos, q = 0;
-            for (int64_t k = c0; k < c1 && rp < t1; ++k) {
-                const uint32_t cw = k == c0 ? (uint32_t)bcast((int32_t)m_cw, i) : b.cigar[k];
-                const uint32_t op = cw & 15u;
-                const int64_t len = cw >> 4;
-                if (op == 0 || op == 7 || op == 8) {
-                    const int64_t e = rp + len < t1 ? rp + len : t1;
-                    for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64) {
-                        const int64_t qq = q + (j - rp);
-                        if (qq < l) {
-                            const uint32_t byte = b.seq[so + (qq >> 1)];
-                            const uint32_t code = (qq & 1) ? (byte & 15u) : (byte >> 4);
-                            if (!test_q || (int32_t)b.qual[qo + qq] >= min_baseq) {
-                                const int ch = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : 4;
-                                atomicAdd(&acc[ch * kTile + t.lead + (int)(j - t0)], 1u);
+    for (int pass = 0; pass < passes; ++pass) {
+        if (kStrand && pass) __syncthreads();               // the first pass's flush has read the window
+        for (int k = threadIdx.x * 4; k < kPlanes * kTile; k += kThreads * 4)
+            *reinterpret_cast<uint4*>(&acc[k]) = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        // A wave takes 64 consecutive reads at a time: lane i loads read i's words (coalesced, independent
+        // loads), then the reads that reach the tile are walked one by one with those words broadcast.
+        for (int64_t g = lo + 64 * (int64_t)wave; g < hi; g += 64 * kWaves) {
+            const int64_t mine = g + lane;
+            const bool have = mine < hi;
+            const int32_t m_pos = have ? b.pos[mine] : 0;
+            const int32_t m_span = have ? span[mine] : 0;
+            const int32_t m_l = have ? b.l_seq[mine] : 0;
+            const int64_t m_c0 = have ? b.cig_off[mine] : 0, m_c1 = have ? b.cig_off[mine + 1] : 0;
+            const int64_t m_so = have ? b.seq_off[mine] : 0, m_qo = have ? b.qual_off[mine] : 0;
+            const uint32_t m_cw = m_c1 > m_c0 ? b.cigar[m_c0] : 0u;        // the first op: the only one of most reads
+            const int32_t m_q0 = m_l > 0 ? (int32_t)b.qual[m_qo] : 0;
+            int32_t m_rev = 0;
+            if (kStrand) m_rev = have ? (int32_t)((flag[mine] >> 4) & 1u) : 0;
+            unsigned long long todo = __ballot(have && (int64_t)m_pos + m_span > t0 &&
+                                               (!kStrand || packed || m_rev == pass));
+            while (todo) {
+                const int i = __ffsll(todo) - 1;
+                todo &= todo - 1;
+                const int64_t pos = bcast(m_pos, i), l = bcast(m_l, i);
+                const int64_t c0 = bcast64(m_c0, i), c1 = bcast64(m_c1, i);
+                const int64_t so = bcast64(m_so, i), qo = bcast64(m_qo, i);
+                const bool test_q = min_baseq > 0 && !(l > 0 && bcast(m_q0, i) == 0xFF);
+                uint32_t one = 1u;
+                if (kStrand) one = packed && bcast(m_rev, i) ? 0x10000u : 1u;
+                int64_t rp = pos, q = 0;
+                for (int64_t k = c0; k < c1 && rp < t1; ++k) {
+                    const uint32_t cw = k == c0 ? (uint32_t)bcast((int32_t)m_cw, i) : b.cigar[k];
+                    const uint32_t op = cw & 15u;
+                    const int64_t len = cw >> 4;
+                    if (op == 0 || op == 7 || op == 8) {
+                        const int64_t e = rp + len < t1 ? rp + len : t1;
+                        for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64) {
+                            const int64_t qq = q + (j - rp);
+                            if (qq < l) {
+                                const uint32_t byte = b.seq[so + (qq >> 1)];
+                                const uint32_t code = (qq & 1) ? (byte & 15u) : (byte >> 4);
+                                if (!test_q || (int32_t)b.qual[qo + qq] >= min_baseq) {
+                                    const int ch = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : 4;
+                                    atomicAdd(&acc[ch * kTile + t.lead + (int)(j - t0)], one);
+                                }
                             }
                         }
+                        rp += len;
+                        q += len;
+                    } else if (op == 2) {
+                        const int64_t e = rp + len < t1 ? rp + len : t1;
+                        for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64)
+                            atomicAdd(&acc[5 * kTile + t.lead + (int)(j - t0)], one);
+                        rp += len;
+                    } else if (op == 3) {
+                        rp += len;
+                    } else if (op == 1 || op == 4) {
+                        q += len;
                     }
-                    rp += len;
-                    q += len;
-                } else if (op == 2) {
-                    const int64_t e = rp + len < t1 ? rp + len : t1;
-                    for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64)
-                        atomicAdd(&acc[5 * kTile + t.lead + (int)(j - t0)], 1u);
-                    rp += len;
-                } else if (op == 3) {
-                    rp += len;
-                } else if (op == 1 || op == 4) {
-                    q += len;
+                }
+            }
+        }
+        __syncthreads();
+        const int first = t.lead, last = t.lead + t.n;          // the tile's part of the window
+#pragma unroll
+        for (int c = 0; c < kPlanes; ++c) {
+            uint32_t* g = planes + c * stride + (t.out - t.lead);   // 16-byte aligned
+            uint32_t* gr = kStrand ? rev + c * stride + (t.out - t.lead) : nullptr;
+            for (int k = threadIdx.x * 4; k < kTile; k += kThreads * 4) {
+                uint4 v = *reinterpret_cast<const uint4*>(&acc[c * kTile + k]);
+                if (!(v.x | v.y | v.z | v.w)) continue;
+                uint4 r = make_uint4(0, 0, 0, 0);               // the reverse strand's share of v
+                if (kStrand) {
+                    if (packed) {
+                        r = make_uint4(v.x >> 16, v.y >> 16, v.z >> 16, v.w >> 16);
+                        v = make_uint4((v.x & 0xFFFFu) + r.x, (v.y & 0xFFFFu) + r.y, (v.z & 0xFFFFu) + r.z,
+                                       (v.w & 0xFFFFu) + r.w);
+                    } else if (pass) {
+                        r = v;
+                    }
+                }
+                if (k >= first && k + 4 <= last) {
+                    uint4 o = *reinterpret_cast<const uint4*>(g + k);
+                    o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+                    *reinterpret_cast<uint4*>(g + k) = o;
+                    if (kStrand && (r.x | r.y | r.z | r.w)) {
+                        uint4 p = *reinterpret_cast<const uint4*>(gr + k);
+                        p.x += r.x; p.y += r.y; p.z += r.z; p.w += r.w;
+                        *reinterpret_cast<uint4*>(gr + k) = p;
+                    }
+                } else {
+                    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+                    const uint32_t er[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (e[i] && k + i >= first && k + i < last) {
+                            g[k + i] += e[i];
+                            if (kStrand && er[i]) gr[k + i] += er[i];
+                        }
                 }
             }
         }
     }
-    __syncthreads();
-    const int first = t.lead, last = t.lead + t.n;          // the tile's part of the window
-#pragma unroll
-    for (int c = 0; c < kPlanes; ++c) {
-        uint32_t* g = planes + c * stride + (t.out - t.lead);   // 16-byte aligned
-        for (int k = threadIdx.x * 4; k < kTile; k += kThreads * 4) {
-            const uint4 v = *reinterpret_cast<const uint4*>(&acc[c * kTile + k]);
-            if (!(v.x | v.y | v.z | v.w)) continue;
-            if (k >= first && k + 4 <= last) {
-                uint4 o = *reinterpret_cast<const uint4*>(g + k);
-                o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
-                *reinterpret_cast<uint4*>(g + k) = o;
-            } else {
-                const uint32_t e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (e[i] && k + i >= first && k + i < last) g[k + i] += e[i];
-            }
-        }
-    }
+}
+
+__global__ __launch_bounds__(kThreads) void bases_pileup_kernel(Batch b, const int32_t* __restrict__ span,
+                                                               const Tile* __restrict__ tiles,
+                                                               const int32_t* __restrict__ order, int32_t max_span,
+                                                               int32_t min_baseq, uint32_t* __restrict__ planes,
+                                                               int64_t stride) {
+    pileup_tile<false>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr);
+}
+
+// The strand instantiation: flag[n] beside the batch's per-read columns, rev
+// the reverse planes (indexed like planes).
+__global__ __launch_bounds__(kThreads) void bases_pileup_strand_kernel(Batch b, const int32_t* __restrict__ span,
+                                                                      const Tile* __restrict__ tiles,
+                                                                      const int32_t* __restrict__ order,
+                                                                      int32_t max_span, int32_t min_baseq,
+                                                                      uint32_t* __restrict__ planes, int64_t stride,
+                                                                      const uint16_t* __restrict__ flag,
+                                                                      uint32_t* __restrict__ rev) {
+    pileup_tile<true>(b, span, tiles, order, max_span, min_baseq, planes, stride, flag, rev);
 }
 
 // depth = A + C + G + T + DEL; the base allele is ref (0..3) where given,
@@ -296,13 +361,54 @@ __device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ plan
     return fm;
 }
 
-__global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* __restrict__ planes, int64_t stride,
-                                                              const uint8_t* __restrict__ ref,
-                                                              const Tile* __restrict__ tiles, SiteArgs s,
-                                                              int32_t* __restrict__ counts) {
+// The strand predicate (mc_bases_sites_strand): a site needs one allele besides
+// the base allele that passes min_count and min_ppm and is seen min_alt times on
+// each strand (r: the reverse counts; forward = total - reverse).  With
+// min_alt == 0 this is is_site: both count tests are monotone in the count, so
+// some allele passes them iff the strongest does.
+__device__ __forceinline__ bool is_site_strand(const uint32_t (&a)[5], const uint32_t (&r)[5], int ref,
+                                               const SiteArgs& s, uint32_t min_alt) {
+    const unsigned long long depth = (unsigned long long)a[0] + a[1] + a[2] + a[3] + a[4];
+    int base = 0;
+    if (ref >= 0 && ref < 4) {
+        base = ref;
+    } else {
+#pragma unroll
+        for (int i = 1; i < 5; ++i)
+            if (a[i] > a[base]) base = i;
+    }
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+        any = any || (i != base && a[i] >= s.min_count && a[i] * 1000000ull >= s.min_ppm * depth &&
+                      r[i] >= min_alt && a[i] - r[i] >= min_alt);
+    return depth >= s.min_depth && any;
+}
+
+__device__ __forceinline__ uint32_t site_flags_strand(const uint32_t* __restrict__ planes,
+                                                      const uint32_t* __restrict__ rev, int64_t stride,
+                                                      const uint8_t* __restrict__ ref, const Tile& t,
+                                                      const SiteArgs& s, uint32_t min_alt) {
+    uint32_t fm = 0;
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const int k = r * kThreads + (int)threadIdx.x;
+        if (k < t.n) {
+            const int64_t i = t.out + k;
+            const uint32_t a[5] = {planes[i], planes[stride + i], planes[2 * stride + i], planes[3 * stride + i],
+                                   planes[5 * stride + i]};
+            const uint32_t b[5] = {rev[i], rev[stride + i], rev[2 * stride + i], rev[3 * stride + i],
+                                   rev[5 * stride + i]};
+            fm |= (uint32_t)is_site_strand(a, b, ref ? (int)ref[i] : 4, s, min_alt) << r;
+        }
+    }
+    return fm;
+}
+
+// The tile's site count from its threads' flag words.
+__device__ __forceinline__ void sites_count_tile(uint32_t fm, int32_t* __restrict__ counts) {
     __shared__ int32_t wsum[kWaves];
-    const Tile t = tiles[blockIdx.x];
-    int32_t c = __popc(site_flags(planes, stride, ref, t, s));
+    int32_t c = __popc(fm);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
@@ -312,6 +418,63 @@ __global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* _
         for (int i = 0; i < kWaves; ++i) sum += wsum[i];
         counts[blockIdx.x] = sum;
     }
+}
+
+// The tile's sites from its threads' flag words: positions and counts in
+// position order; site_rev (or null): the reverse counts beside them.
+__device__ __forceinline__ void sites_emit_tile(uint32_t fm, const Tile& t, const uint32_t* __restrict__ planes,
+                                                const uint32_t* __restrict__ rev, int64_t stride,
+                                                const int64_t* __restrict__ base, int64_t* __restrict__ site_pos,
+                                                uint32_t* __restrict__ site_counts,
+                                                uint32_t* __restrict__ site_rev) {
+    __shared__ int32_t wcnt[kRounds][kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int32_t rank[kRounds];                                  // sites of this round in lower lanes of the wave
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        const unsigned long long m = __ballot((fm >> r) & 1);
+        rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        if (lane == 0) wcnt[r][wave] = __popcll(m);
+    }
+    __syncthreads();
+    int64_t run = base[blockIdx.x];                         // positions ascend with (round, wave, lane)
+#pragma unroll
+    for (int r = 0; r < kRounds; ++r) {
+        int64_t mine = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            if (w == wave) mine = run;
+            run += wcnt[r][w];
+        }
+        if ((fm >> r) & 1) {
+            const int k = r * kThreads + (int)threadIdx.x;
+            const int64_t o = mine + rank[r], i = t.out + k;
+            site_pos[o] = t.rel + k;
+#pragma unroll
+            for (int c = 0; c < kPlanes; ++c) site_counts[o * kPlanes + c] = planes[c * stride + i];
+            if (site_rev) {
+#pragma unroll
+                for (int c = 0; c < kPlanes; ++c) site_rev[o * kPlanes + c] = rev[c * stride + i];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* __restrict__ planes, int64_t stride,
+                                                              const uint8_t* __restrict__ ref,
+                                                              const Tile* __restrict__ tiles, SiteArgs s,
+                                                              int32_t* __restrict__ counts) {
+    const Tile t = tiles[blockIdx.x];
+    sites_count_tile(site_flags(planes, stride, ref, t, s), counts);
+}
+
+__global__ __launch_bounds__(kThreads) void sites_count_strand_kernel(const uint32_t* __restrict__ planes,
+                                                                     const uint32_t* __restrict__ rev, int64_t stride,
+                                                                     const uint8_t* __restrict__ ref,
+                                                                     const Tile* __restrict__ tiles, SiteArgs s,
+                                                                     uint32_t min_alt, int32_t* __restrict__ counts) {
+    const Tile t = tiles[blockIdx.x];
+    sites_count_tile(site_flags_strand(planes, rev, stride, ref, t, s, min_alt), counts);
 }
 
 // One workgroup.  base[i] = sum of counts[0, i) for i <= n_tiles, then
@@ -365,35 +528,22 @@ __global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __
                                                              const int64_t* __restrict__ base,
                                                              int64_t* __restrict__ site_pos,
                                                              uint32_t* __restrict__ site_counts) {
-    __shared__ int32_t wcnt[kRounds][kWaves];
     const Tile t = tiles[blockIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t fm = site_flags(planes, stride, ref, t, s);
-    int32_t rank[kRounds];                                  // sites of this round in lower lanes of the wave
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const unsigned long long m = __ballot((fm >> r) & 1);
-        rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-        if (lane == 0) wcnt[r][wave] = __popcll(m);
-    }
-    __syncthreads();
-    int64_t run = base[blockIdx.x];                         // positions ascend with (round, wave, lane)
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        int64_t mine = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w == wave) mine = run;
-            run += wcnt[r][w];
-        }
-        if ((fm >> r) & 1) {
-            const int k = r * kThreads + (int)threadIdx.x;
-            const int64_t o = mine + rank[r], i = t.out + k;
-            site_pos[o] = t.rel + k;
-#pragma unroll
-            for (int c = 0; c < kPlanes; ++c) site_counts[o * kPlanes + c] = planes[c * stride + i];
-        }
-    }
+    sites_emit_tile(site_flags(planes, stride, ref, t, s), t, planes, nullptr, stride, base, site_pos, site_counts,
+                    nullptr);
+}
+
+__global__ __launch_bounds__(kThreads) void sites_emit_strand_kernel(const uint32_t* __restrict__ planes,
+                                                                    const uint32_t* __restrict__ rev, int64_t stride,
+                                                                    const uint8_t* __restrict__ ref,
+                                                                    const Tile* __restrict__ tiles, SiteArgs s,
+                                                                    uint32_t min_alt, const int64_t* __restrict__ base,
+                                                                    int64_t* __restrict__ site_pos,
+                                                                    uint32_t* __restrict__ site_counts,
+                                                                    uint32_t* __restrict__ site_rev) {
+    const Tile t = tiles[blockIdx.x];
+    sites_emit_tile(site_flags_strand(planes, rev, stride, ref, t, s, min_alt), t, planes, rev, stride, base,
+                    site_pos, site_counts, site_rev);
 }
 
 // ---- consensus (the rule is the header's, "Consensus") ----------------------
@@ -708,6 +858,12 @@ struct mc_bases {
     bool have_cons_ins = false;
     hipEvent_t iev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms_ins_extract = 0, ms_ins_group = 0, ms_ins_cons = 0;
+    // strand (opt-in, mc_bases_track_strand): the reverse-strand reads' planes beside the totals
+    bool strand_next = false, strand = false;
+    Buf<uint32_t> rev;                   // [6][stride], indexed like planes
+    Buf<uint16_t> rflag;                 // the flags of the host batch in flight
+    bool have_sites_rev = false;         // the sites are mc_bases_sites_strand's: site_rev is filled
+    Buf<uint32_t> site_rev;
     ~mc_bases() {
         for (auto& e : iev)
             if (e) (void)hipEventDestroy(e);
@@ -771,6 +927,8 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->have_cons = false;
     h->have_cons_ins = false;
     h->tracking = false;
+    h->strand = false;
+    h->have_sites_rev = false;
 
     // ---- tile table (host): a tile never spans two segments
     std::vector<Tile> tiles;
@@ -823,12 +981,17 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     if (T) HIP_TRY(hipMemcpyAsync(h->order.p, order.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->seg_tile.p, seg_tile.data(), ((size_t)S + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(h->planes.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
+    if (h->strand_next) {
+        HIP_TRY(h->rev.reserve((size_t)(kPlanes * stride)));
+        HIP_TRY(hipMemsetAsync(h->rev.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
+    }
     if (h->track_next) {                          // the events of an earlier begin are gone
         HIP_TRY(h->tile_total.reserve((size_t)T));
         if (T) HIP_TRY(hipMemsetAsync(h->tile_total.p, 0, (size_t)T * 4, st));
     }
     HIP_TRY(hipStreamSynchronize(st));            // the host vectors are released
     h->tracking = h->track_next;
+    h->strand = h->strand_next;
     h->n_events = 0;
     h->ins_from_set = false;
     h->sorted_valid = h->have_weight = false;
@@ -1018,16 +1181,33 @@ int ins_encode(mc_bases* h, const SiteArgs& sa, InsTable& tab) {
 
 }  // namespace
 
-extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
-                                  const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
-                                  const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
-                                  const uint8_t* qual) {
+namespace {
+
+// The pileup launch of a batch over tiles [first, first + nt) of the sorted
+// order; flag: the reads' flags in device memory on a handle that tracks strand.
+void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span, const uint16_t* flag) {
+    if (h->strand)
+        hipLaunchKernelGGL(bases_pileup_strand_kernel, dim3((unsigned)nt), dim3(kThreads), 0, h->stream, b, h->span.p,
+                           h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride, flag,
+                           h->rev.p);
+    else
+        hipLaunchKernelGGL(bases_pileup_kernel, dim3((unsigned)nt), dim3(kThreads), 0, h->stream, b, h->span.p,
+                           h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride);
+}
+
+// mc_bases_add_batch (flagged false) and mc_bases_add_batch_flags (true).
+int add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos, const int64_t* cig_off,
+              const uint32_t* cigar, const int32_t* l_seq, const int64_t* seq_off, const uint8_t* seq,
+              const int64_t* qual_off, const uint8_t* qual, bool flagged, const uint16_t* flag) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
     MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
+    MC_REQUIRE(flagged || !h->strand, MC_E_STATE,
+               "the handle tracks strand: the reads' flags are needed (mc_bases_add_batch_flags)");
     MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
     if (n == 0) return MC_OK;
-    MC_REQUIRE(tid && pos && cig_off && l_seq && seq_off && qual_off, MC_E_INVALID, "null read arrays");
+    MC_REQUIRE(tid && pos && cig_off && l_seq && seq_off && qual_off && (flag || !h->strand), MC_E_INVALID,
+               "null read arrays");
     const int64_t n_words = cig_off[n], seq_bytes = seq_off[n], qual_bytes = qual_off[n];
     MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
     MC_REQUIRE((n_words == 0 || cigar) && (seq_bytes == 0 || seq) && (qual_bytes == 0 || qual), MC_E_INVALID,
@@ -1046,6 +1226,7 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     HIP_TRY(h->cigar.reserve((size_t)n_words));
     HIP_TRY(h->seq.reserve((size_t)seq_bytes));
     HIP_TRY(h->qual.reserve((size_t)qual_bytes));
+    if (h->strand) HIP_TRY(h->rflag.reserve((size_t)n));
     hipStream_t st = h->stream;
     const auto up = [st](void* d, const void* s, size_t bytes) {
         return bytes ? hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
@@ -1059,6 +1240,7 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     HIP_TRY(up(h->cigar.p, cigar, (size_t)n_words * 4));
     HIP_TRY(up(h->seq.p, seq, (size_t)seq_bytes));
     HIP_TRY(up(h->qual.p, qual, (size_t)qual_bytes));
+    if (h->strand) HIP_TRY(up(h->rflag.p, flag, (size_t)n * 2));
     h->pin[0] = kNoBad;
     h->pin[1] = 0;
     HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
@@ -1093,9 +1275,7 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
                                        std::make_pair(tid[n - 1], (int64_t)pos[n - 1] + max_span));
     if (max_span > 0 && t_lo < t_hi) {
-        hipLaunchKernelGGL(bases_pileup_kernel, dim3((unsigned)(t_hi - t_lo)), dim3(kThreads), 0, st, b, h->span.p,
-                           h->tiles.p, h->order.p + (t_lo - h->tile_key.begin()), max_span, h->min_baseq,
-                           h->planes.p, h->stride);
+        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, h->rflag.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[3], st));
@@ -1120,6 +1300,22 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
     return MC_OK;
 }
 
+}  // namespace
+
+extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                                  const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
+                                  const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
+                                  const uint8_t* qual) {
+    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, false, nullptr);
+}
+
+extern "C" int mc_bases_add_batch_flags(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                                        const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
+                                        const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
+                                        const uint8_t* qual, const uint16_t* flag) {
+    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, true, flag);
+}
+
 namespace {
 
 // ends[0..3] = the first and the last read's (tid, pos): the few words of a
@@ -1133,19 +1329,20 @@ __global__ void bases_ends_kernel(Batch b, int32_t* __restrict__ ends) {
     }
 }
 
-}  // namespace
-
-extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
-                                         const int64_t* d_cig_off, const uint32_t* d_cigar, int64_t n_words,
-                                         const int32_t* d_l_seq, const int64_t* d_seq_off, const uint8_t* d_seq,
-                                         int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
-                                         int64_t qual_bytes) {
+// mc_bases_add_batch_device (flagged false) and mc_bases_add_batch_device_flags (true).
+int add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos, const int64_t* d_cig_off,
+                     const uint32_t* d_cigar, int64_t n_words, const int32_t* d_l_seq, const int64_t* d_seq_off,
+                     const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
+                     int64_t qual_bytes, bool flagged, const uint16_t* d_flag) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
     MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
+    MC_REQUIRE(flagged || !h->strand, MC_E_STATE,
+               "the handle tracks strand: the reads' flags are needed (mc_bases_add_batch_device_flags)");
     MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
     if (n == 0) return MC_OK;
-    MC_REQUIRE(d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off, MC_E_INVALID, "null read arrays");
+    MC_REQUIRE(d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off && (d_flag || !h->strand),
+               MC_E_INVALID, "null read arrays");
     MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
     MC_REQUIRE((n_words == 0 || d_cigar) && (seq_bytes == 0 || d_seq) && (qual_bytes == 0 || d_qual), MC_E_INVALID,
                "null arena");
@@ -1219,9 +1416,7 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
     const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
                                        std::make_pair(ends[2], (int64_t)ends[3] + max_span));
     if (max_span > 0 && t_lo < t_hi) {
-        hipLaunchKernelGGL(bases_pileup_kernel, dim3((unsigned)(t_hi - t_lo)), dim3(kThreads), 0, st, b, h->span.p,
-                           h->tiles.p, h->order.p + (t_lo - h->tile_key.begin()), max_span, h->min_baseq,
-                           h->planes.p, h->stride);
+        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, d_flag);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[3], st));
@@ -1244,6 +1439,26 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
     h->have_cons_ins = false;
     h->tab_user.valid = h->tab_cons.valid = false;
     return MC_OK;
+}
+
+}  // namespace
+
+extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                                         const int64_t* d_cig_off, const uint32_t* d_cigar, int64_t n_words,
+                                         const int32_t* d_l_seq, const int64_t* d_seq_off, const uint8_t* d_seq,
+                                         int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
+                                         int64_t qual_bytes) {
+    return add_batch_device(h, n, d_tid, d_pos, d_cig_off, d_cigar, n_words, d_l_seq, d_seq_off, d_seq, seq_bytes,
+                            d_qual_off, d_qual, qual_bytes, false, nullptr);
+}
+
+extern "C" int mc_bases_add_batch_device_flags(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                                               const int64_t* d_cig_off, const uint32_t* d_cigar, int64_t n_words,
+                                               const int32_t* d_l_seq, const int64_t* d_seq_off,
+                                               const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off,
+                                               const uint8_t* d_qual, int64_t qual_bytes, const uint16_t* d_flag) {
+    return add_batch_device(h, n, d_tid, d_pos, d_cig_off, d_cigar, n_words, d_l_seq, d_seq_off, d_seq, seq_bytes,
+                            d_qual_off, d_qual, qual_bytes, true, d_flag);
 }
 
 extern "C" int mc_bases_seg_off(const mc_bases* h, int64_t* seg_off) {
@@ -1278,15 +1493,21 @@ extern "C" int mc_bases_device(const mc_bases* h, const uint32_t** d_planes, int
     return MC_OK;
 }
 
-extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
-                              const uint8_t* ref, int64_t* n_sites) {
-    MC_REQUIRE(h && n_sites, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+namespace {
+
+// mc_bases_sites (min_alt < 0: the plain predicate and kernels) and
+// mc_bases_sites_strand (min_alt >= 0) share everything but the count and emit
+// launches.
+int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, int64_t min_alt, const uint8_t* ref,
+          int64_t* n_sites) {
+    const bool strand = min_alt >= 0;
     MC_REQUIRE(min_depth >= 0 && min_count >= 0 && min_ppm >= 0 && min_ppm <= 1000000, MC_E_INVALID,
                "site thresholds out of range (min_depth %lld, min_count %lld, min_ppm %lld of 10^6)",
                (long long)min_depth, (long long)min_count, (long long)min_ppm);
     h->have_sites = false;
+    h->have_sites_rev = false;
     const int64_t T = h->n_tiles, S = h->S;
+    const uint32_t k_alt = (uint32_t)std::min<int64_t>(std::max<int64_t>(min_alt, 0), UINT32_MAX);
     const SiteArgs sa{(unsigned long long)min_depth, (unsigned long long)min_count, (unsigned long long)min_ppm};
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->counts.reserve((size_t)T));
@@ -1301,8 +1522,12 @@ extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count,
     }
     HIP_TRY(hipEventRecord(h->ev[4], st));
     if (T) {
-        hipLaunchKernelGGL(sites_count_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
-                           h->tiles.p, sa, h->counts.p);
+        if (strand)
+            hipLaunchKernelGGL(sites_count_strand_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
+                               h->rev.p, h->stride, d_ref, h->tiles.p, sa, k_alt, h->counts.p);
+        else
+            hipLaunchKernelGGL(sites_count_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride,
+                               d_ref, h->tiles.p, sa, h->counts.p);
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->counts.p, T, h->base.p,
@@ -1315,9 +1540,15 @@ extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count,
     MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "site count %lld out of range", (long long)total);
     HIP_TRY(h->site_pos.reserve((size_t)total));
     HIP_TRY(h->site_counts.reserve((size_t)total * kPlanes));
+    if (strand) HIP_TRY(h->site_rev.reserve((size_t)total * kPlanes));
     if (T) {
-        hipLaunchKernelGGL(sites_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
-                           h->tiles.p, sa, h->base.p, h->site_pos.p, h->site_counts.p);
+        if (strand)
+            hipLaunchKernelGGL(sites_emit_strand_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
+                               h->rev.p, h->stride, d_ref, h->tiles.p, sa, k_alt, h->base.p, h->site_pos.p,
+                               h->site_counts.p, h->site_rev.p);
+        else
+            hipLaunchKernelGGL(sites_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride,
+                               d_ref, h->tiles.p, sa, h->base.p, h->site_pos.p, h->site_counts.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[5], st));
@@ -1325,7 +1556,97 @@ extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count,
     HIP_TRY(hipEventElapsedTime(&h->ms_sites, h->ev[4], h->ev[5]));   // (the 8-byte read-back included)
     h->n_sites = total;
     h->have_sites = true;
+    h->have_sites_rev = strand;
     *n_sites = total;
+    return MC_OK;
+}
+
+}  // namespace
+
+extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                              const uint8_t* ref, int64_t* n_sites) {
+    MC_REQUIRE(h && n_sites, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    return sites(h, min_depth, min_count, min_ppm, -1, ref, n_sites);
+}
+
+extern "C" int mc_bases_sites_strand(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                                     int64_t min_alt_strand, const uint8_t* ref, int64_t* n_sites) {
+    MC_REQUIRE(h && n_sites, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
+    MC_REQUIRE(min_alt_strand >= 0, MC_E_INVALID, "min_alt_strand %lld is negative", (long long)min_alt_strand);
+    return sites(h, min_depth, min_count, min_ppm, min_alt_strand, ref, n_sites);
+}
+
+extern "C" int mc_bases_sites_get_reverse(const mc_bases* h, int64_t first, int64_t count, uint32_t* rev_counts) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_sites && h->have_sites_rev, MC_E_STATE,
+               "no strand sites computed (call mc_bases_sites_strand)");
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->n_sites && count <= h->n_sites - first, MC_E_INVALID,
+               "sites [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count,
+               (long long)h->n_sites);
+    MC_REQUIRE(count == 0 || rev_counts, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(rev_counts, h->site_rev.p + first * kPlanes, (size_t)count * kPlanes * 4,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_track_strand(mc_bases* h, int on) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(on == 0 || on == 1, MC_E_INVALID, "on must be 0 or 1, not %d", on);
+    h->strand_next = on != 0;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_get_reverse(const mc_bases* h, int64_t first, int64_t count, uint32_t* out) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
+               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
+               (long long)count, (long long)h->N);
+    MC_REQUIRE(count == 0 || out, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    for (int c = 0; c < kPlanes; ++c)
+        HIP_TRY(hipMemcpyAsync(out + (size_t)c * (size_t)count, h->rev.p + c * h->stride + first, (size_t)count * 4,
+                               hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_reverse_device(const mc_bases* h, const uint32_t** d_rev, int64_t* stride, int64_t* n) {
+    MC_REQUIRE(h && d_rev && stride && n, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
+    *d_rev = h->rev.p;
+    *stride = h->stride;
+    *n = h->N;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_set_strand(mc_bases* h, int64_t first, int64_t count, const uint32_t* total,
+                                   const uint32_t* rev) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
+               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
+               (long long)count, (long long)h->N);
+    MC_REQUIRE(count == 0 || (total && rev), MC_E_INVALID, "null in");
+    for (int64_t k = 0; k < kPlanes * count; ++k)
+        MC_REQUIRE(rev[k] <= total[k], MC_E_INVALID, "channel %lld, position %lld: reverse count %u exceeds total %u",
+                   (long long)(k / count), (long long)(first + k % count), rev[k], total[k]);
+    const int rc = mc_bases_set(h, first, count, total);
+    if (rc != MC_OK || count == 0) return rc;
+    for (int c = 0; c < kPlanes; ++c)
+        HIP_TRY(hipMemcpyAsync(h->rev.p + c * h->stride + first, rev + (size_t)c * (size_t)count, (size_t)count * 4,
+                               hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return MC_OK;
 }
 

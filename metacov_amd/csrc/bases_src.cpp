@@ -49,6 +49,7 @@ struct mc_bases_src {
     std::vector<int64_t> cig_off, seq_off, qual_off;
     std::vector<uint32_t> cigar;
     std::vector<uint8_t> seq, qual;
+    std::vector<uint16_t> flag;          // (mc_bases_src_flags: the strand is flag & 0x10)
     int64_t n_bases = 0;
     ~mc_bases_src() {
         if (prod.joinable()) prod.join();
@@ -57,6 +58,7 @@ struct mc_bases_src {
         tid.clear();
         pos.clear();
         l_seq.clear();
+        flag.clear();
         cig_off.assign(1, 0);
         seq_off.assign(1, 0);
         qual_off.assign(1, 0);
@@ -202,6 +204,7 @@ int next_batch(mc_bases_src* s, int64_t max_reads, int64_t max_bases) {
         s->tid.push_back(tid);
         s->pos.push_back(pos);
         s->l_seq.push_back(l_seq);
+        s->flag.push_back((uint16_t)flag);
         const size_t w0 = s->cigar.size();
         s->cigar.resize(w0 + nc);
         for (uint32_t k = 0; k < nc; ++k) s->cigar[w0 + k] = rd32(cig + 4 * k);
@@ -280,6 +283,12 @@ extern "C" int mc_bases_src_batch(const mc_bases_src* s, const int32_t** tid, co
     if (seq) *seq = s->seq.data();
     if (qual_off) *qual_off = s->qual_off.data();
     if (qual) *qual = s->qual.data();
+    return MC_OK;
+}
+
+extern "C" int mc_bases_src_flags(const mc_bases_src* s, const uint16_t** flag) {
+    MC_REQUIRE(s && flag, MC_E_INVALID, "null argument");
+    *flag = s->flag.data();
     return MC_OK;
 }
 
