@@ -43,18 +43,9 @@
 
 #include "bgzf.h"
 #include "inflate.h"
+#include "tile_util.h"
 
 using namespace mc::bgzf;
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
 
 namespace {
 

@@ -71,16 +71,17 @@
 
 #include "../../include/metacov_amd.h"
 #include "common.h"
+#include "tile_util.h"
 
 namespace {
+
+using mc::kScanThreads;
 
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kTile = 2048;                         // positions per tile: 6 x 4 B x 2048 = 48 KiB of LDS
 constexpr int kPlanes = 6;                          // A, C, G, T, N, DEL
 constexpr int kRounds = kTile / kThreads;           // positions per thread of the sites kernels
-constexpr int kScanThreads = 1024;
-constexpr int kScanWidth = kScanThreads * 4;        // tiles per iteration of the scan
 constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_runs_compute's bound
 constexpr unsigned long long kNoBad = ~0ull;
 constexpr uint32_t kQueryOps = 0x193u;              // M I S = X advance the query
@@ -324,50 +325,17 @@ __global__ __launch_bounds__(kThreads) void bases_pileup_strand_kernel(Batch b, 
 }
 
 // depth = A + C + G + T + DEL; the base allele is ref (0..3) where given,
-// else the allele with the highest count (ties: the lowest channel); alt the
-// highest count among the other four.  64-bit integers only.
-__device__ __forceinline__ bool is_site(const uint32_t (&a)[5], int ref, const SiteArgs& s) {
-    const unsigned long long depth = (unsigned long long)a[0] + a[1] + a[2] + a[3] + a[4];
-    int base = 0;
-    if (ref >= 0 && ref < 4) {
-        base = ref;
-    } else {
-#pragma unroll
-        for (int i = 1; i < 5; ++i)
-            if (a[i] > a[base]) base = i;
-    }
-    unsigned long long alt = 0;
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-        if (i != base && a[i] > alt) alt = a[i];
-    return depth >= s.min_depth && alt >= s.min_count && alt * 1000000ull >= s.min_ppm * depth;
-}
-
-// Bit r of the result: position r * kThreads + threadIdx.x of tile t is a site.
-__device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ planes, int64_t stride,
-                                               const uint8_t* __restrict__ ref, const Tile& t,
-                                               const SiteArgs& s) {
-    uint32_t fm = 0;
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const int k = r * kThreads + (int)threadIdx.x;
-        if (k < t.n) {
-            const int64_t i = t.out + k;
-            const uint32_t a[5] = {planes[i], planes[stride + i], planes[2 * stride + i], planes[3 * stride + i],
-                                   planes[5 * stride + i]};
-            fm |= (uint32_t)is_site(a, ref ? (int)ref[i] : 4, s) << r;
-        }
-    }
-    return fm;
-}
-
-// The strand predicate (mc_bases_sites_strand): a site needs one allele besides
-// the base allele that passes min_count and min_ppm and is seen min_alt times on
+// else the allele with the highest count (ties: the lowest channel).  64-bit
+// integers only.  The plain predicate (kStrand false; r and min_alt unused): alt,
+// the highest count among the other four, passes min_count and min_ppm.  The
+// strand predicate (mc_bases_sites_strand): a site needs one allele besides the
+// base allele that passes min_count and min_ppm and is seen min_alt times on
 // each strand (r: the reverse counts; forward = total - reverse).  With
-// min_alt == 0 this is is_site: both count tests are monotone in the count, so
-// some allele passes them iff the strongest does.
-__device__ __forceinline__ bool is_site_strand(const uint32_t (&a)[5], const uint32_t (&r)[5], int ref,
-                                               const SiteArgs& s, uint32_t min_alt) {
+// min_alt == 0 this is the plain predicate: both count tests are monotone in
+// the count, so some allele passes them iff the strongest does.
+template <bool kStrand>
+__device__ __forceinline__ bool is_site(const uint32_t (&a)[5], const uint32_t (&r)[5], int ref, const SiteArgs& s,
+                                        uint32_t min_alt) {
     const unsigned long long depth = (unsigned long long)a[0] + a[1] + a[2] + a[3] + a[4];
     int base = 0;
     if (ref >= 0 && ref < 4) {
@@ -376,6 +344,13 @@ __device__ __forceinline__ bool is_site_strand(const uint32_t (&a)[5], const uin
 #pragma unroll
         for (int i = 1; i < 5; ++i)
             if (a[i] > a[base]) base = i;
+    }
+    if (!kStrand) {
+        unsigned long long alt = 0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+            if (i != base && a[i] > alt) alt = a[i];
+        return depth >= s.min_depth && alt >= s.min_count && alt * 1000000ull >= s.min_ppm * depth;
     }
     bool any = false;
 #pragma unroll
@@ -385,10 +360,12 @@ __device__ __forceinline__ bool is_site_strand(const uint32_t (&a)[5], const uin
     return depth >= s.min_depth && any;
 }
 
-__device__ __forceinline__ uint32_t site_flags_strand(const uint32_t* __restrict__ planes,
-                                                      const uint32_t* __restrict__ rev, int64_t stride,
-                                                      const uint8_t* __restrict__ ref, const Tile& t,
-                                                      const SiteArgs& s, uint32_t min_alt) {
+// Bit r of the result: position r * kThreads + threadIdx.x of tile t is a site.
+// rev is read only when kStrand.
+template <bool kStrand>
+__device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ planes, const uint32_t* __restrict__ rev,
+                                               int64_t stride, const uint8_t* __restrict__ ref, const Tile& t,
+                                               const SiteArgs& s, uint32_t min_alt) {
     uint32_t fm = 0;
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
@@ -397,9 +374,12 @@ __device__ __forceinline__ uint32_t site_flags_strand(const uint32_t* __restrict
             const int64_t i = t.out + k;
             const uint32_t a[5] = {planes[i], planes[stride + i], planes[2 * stride + i], planes[3 * stride + i],
                                    planes[5 * stride + i]};
-            const uint32_t b[5] = {rev[i], rev[stride + i], rev[2 * stride + i], rev[3 * stride + i],
-                                   rev[5 * stride + i]};
-            fm |= (uint32_t)is_site_strand(a, b, ref ? (int)ref[i] : 4, s, min_alt) << r;
+            uint32_t b[5] = {0, 0, 0, 0, 0};
+            if (kStrand) {
+                b[0] = rev[i], b[1] = rev[stride + i], b[2] = rev[2 * stride + i], b[3] = rev[3 * stride + i];
+                b[4] = rev[5 * stride + i];
+            }
+            fm |= (uint32_t)is_site<kStrand>(a, b, ref ? (int)ref[i] : 4, s, min_alt) << r;
         }
     }
     return fm;
@@ -460,12 +440,15 @@ __device__ __forceinline__ void sites_emit_tile(uint32_t fm, const Tile& t, cons
     }
 }
 
+// The plain and the strand kernels of the count and the emit pass: thin, so
+// that a handle that never asks for strand runs kernels without the strand
+// arguments (as bases_pileup_kernel).
 __global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* __restrict__ planes, int64_t stride,
                                                               const uint8_t* __restrict__ ref,
                                                               const Tile* __restrict__ tiles, SiteArgs s,
                                                               int32_t* __restrict__ counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags(planes, stride, ref, t, s), counts);
+    sites_count_tile(site_flags<false>(planes, nullptr, stride, ref, t, s, 0), counts);
 }
 
 __global__ __launch_bounds__(kThreads) void sites_count_strand_kernel(const uint32_t* __restrict__ planes,
@@ -474,52 +457,20 @@ __global__ __launch_bounds__(kThreads) void sites_count_strand_kernel(const uint
                                                                      const Tile* __restrict__ tiles, SiteArgs s,
                                                                      uint32_t min_alt, int32_t* __restrict__ counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags_strand(planes, rev, stride, ref, t, s, min_alt), counts);
+    sites_count_tile(site_flags<true>(planes, rev, stride, ref, t, s, min_alt), counts);
 }
 
 // One workgroup.  base[i] = sum of counts[0, i) for i <= n_tiles, then
-// seg_first[s] = base[seg_tile[s]] for s <= S (runs.hip's scan).
-__global__ __launch_bounds__(kScanThreads) void sites_scan_kernel(const int32_t* __restrict__ counts,
-                                                                 int64_t n_tiles, int64_t* __restrict__ base,
-                                                                 const int64_t* __restrict__ seg_tile, int64_t S,
-                                                                 int64_t* __restrict__ seg_first) {
-    __shared__ int32_t wsum[kScanThreads / 64];
-    __shared__ int64_t carry_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t i0 = 0; i0 < n_tiles; i0 += kScanWidth) {
-        const int64_t i = i0 + 4 * (int64_t)t;
-        int32_t c[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = i + k < n_tiles ? counts[i + k] : 0;
-        const int32_t mine = c[0] + c[1] + c[2] + c[3];     // <= 4 kTile; an iteration's sum < 2^24
-        int32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int32_t wbase = 0, total = 0;
-        for (int w = 0; w < kScanThreads / 64; ++w) {
-            if (w < wave) wbase += wsum[w];
-            total += wsum[w];
-        }
-        int64_t bs = carry_s + wbase + (inc - mine);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (i + k < n_tiles) base[i + k] = bs;
-            bs += c[k];
-        }
-        __syncthreads();                                    // every thread has read carry_s and wsum
-        if (t == 0) carry_s += total;
-        __syncthreads();
-    }
-    if (t == 0) base[n_tiles] = carry_s;
-    __syncthreads();                                        // base[] is visible to this workgroup
-    for (int64_t s = t; s <= S; s += kScanThreads) seg_first[s] = base[seg_tile[s]];
+// seg_first[s] = base[seg_tile[s]] for s <= S (runs.hip's scan kernel).  The
+// scan of the sites, of the insertion rows and of the consensus' two insertion
+// columns; with S = -1 and null segment arrays the scan alone, for the
+// insertion events' counts per tile.
+__global__ __launch_bounds__(kScanThreads) void tile_scan_kernel(const int32_t* __restrict__ counts, int64_t n_tiles,
+                                                                int64_t* __restrict__ base,
+                                                                const int64_t* __restrict__ seg_tile, int64_t S,
+                                                                int64_t* __restrict__ seg_first) {
+    mc::tile_scan(counts, n_tiles, base);
+    for (int64_t s = threadIdx.x; s <= S; s += kScanThreads) seg_first[s] = base[seg_tile[s]];
 }
 
 __global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __restrict__ planes, int64_t stride,
@@ -529,8 +480,8 @@ __global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __
                                                              int64_t* __restrict__ site_pos,
                                                              uint32_t* __restrict__ site_counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags(planes, stride, ref, t, s), t, planes, nullptr, stride, base, site_pos, site_counts,
-                    nullptr);
+    sites_emit_tile(site_flags<false>(planes, nullptr, stride, ref, t, s, 0), t, planes, nullptr, stride, base,
+                    site_pos, site_counts, nullptr);
 }
 
 __global__ __launch_bounds__(kThreads) void sites_emit_strand_kernel(const uint32_t* __restrict__ planes,
@@ -542,7 +493,7 @@ __global__ __launch_bounds__(kThreads) void sites_emit_strand_kernel(const uint3
                                                                     uint32_t* __restrict__ site_counts,
                                                                     uint32_t* __restrict__ site_rev) {
     const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags_strand(planes, rev, stride, ref, t, s, min_alt), t, planes, rev, stride, base,
+    sites_emit_tile(site_flags<true>(planes, rev, stride, ref, t, s, min_alt), t, planes, rev, stride, base,
                     site_pos, site_counts, site_rev);
 }
 
@@ -655,56 +606,17 @@ __global__ __launch_bounds__(kThreads) void cons_call_kernel(const uint32_t* __r
 }
 
 // One workgroup.  For each column c: pre[c][i] = sum of cols[c][0, i) for
-// i <= n_tiles (sites_scan_kernel's scan; a tile's entry is at most kTile, an
-// iteration's sum below 2^24).  Then out_first[s] = pre[7][seg_tile[s]] and
-// rows[s][c] = pre[c][seg_tile[s + 1]] - pre[c][seg_tile[s]]: a segment's
-// tiles are contiguous, an empty segment has none.
+// i <= n_tiles (a tile's entry is at most kTile).  Then out_first[s] =
+// pre[7][seg_tile[s]] and rows[s][c] = pre[c][seg_tile[s + 1]] -
+// pre[c][seg_tile[s]]: a segment's tiles are contiguous, an empty segment has
+// none.
 __global__ __launch_bounds__(kScanThreads) void cons_scan_kernel(const int32_t* __restrict__ cols, int64_t n_tiles,
                                                                 int64_t* __restrict__ pre,
                                                                 const int64_t* __restrict__ seg_tile, int64_t S,
                                                                 int64_t* __restrict__ out_first,
                                                                 int64_t* __restrict__ rows) {
-    __shared__ int32_t wsum[kScanThreads / 64];
-    __shared__ int64_t carry_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    for (int col = 0; col < kConsCols; ++col) {
-        const int32_t* __restrict__ src = cols + col * n_tiles;
-        int64_t* __restrict__ dst = pre + col * (n_tiles + 1);
-        if (t == 0) carry_s = 0;
-        __syncthreads();
-        for (int64_t i0 = 0; i0 < n_tiles; i0 += kScanWidth) {
-            const int64_t i = i0 + 4 * (int64_t)t;
-            int32_t c[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c[k] = i + k < n_tiles ? src[i + k] : 0;
-            const int32_t mine = c[0] + c[1] + c[2] + c[3];
-            int32_t inc = mine;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int32_t o = __shfl_up(inc, off, 64);
-                if (lane >= off) inc += o;
-            }
-            if (lane == 63) wsum[wave] = inc;
-            __syncthreads();
-            int32_t wbase = 0, total = 0;
-            for (int w = 0; w < kScanThreads / 64; ++w) {
-                if (w < wave) wbase += wsum[w];
-                total += wsum[w];
-            }
-            int64_t bs = carry_s + wbase + (inc - mine);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (i + k < n_tiles) dst[i + k] = bs;
-                bs += c[k];
-            }
-            __syncthreads();                                // every thread has read carry_s and wsum
-            if (t == 0) carry_s += total;
-            __syncthreads();
-        }
-        if (t == 0) dst[n_tiles] = carry_s;
-        __syncthreads();                                    // carry_s is free for the next column
-    }
-    // (pre[] is visible to this workgroup after the barrier above)
+    const int t = threadIdx.x;
+    for (int col = 0; col < kConsCols; ++col) mc::tile_scan(cols + col * n_tiles, n_tiles, pre + col * (n_tiles + 1));
     for (int64_t s = t; s <= S; s += kScanThreads) out_first[s] = pre[7 * (n_tiles + 1) + seg_tile[s]];
     for (int64_t j = t; j < S * kConsCols; j += kScanThreads) {
         const int64_t s = j / kConsCols, col = j % kConsCols;
@@ -746,41 +658,11 @@ __global__ __launch_bounds__(kThreads) void cons_emit_kernel(const uint8_t* __re
 
 #include "bases_ins.h"   // the insertion stage's kernels
 
-}  // namespace
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
-
-namespace {
-
 constexpr size_t kArenaPad = 64;   // bytes behind every uploaded array
 
 // grow-only device array, kArenaPad bytes of room behind the n elements asked for
 template <typename T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(n, (size_t)256);
-        hipError_t e = hipMalloc(&p, want * sizeof(T) + kArenaPad);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
+using Buf = mc::Buf<T, kArenaPad>;
 
 // a grouped allele table in device memory (rows sorted by (i, other, len, code))
 struct InsTable {
@@ -876,6 +758,49 @@ struct mc_bases {
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
+
+namespace {
+
+// [first, first + count) lies inside [0, n]; what: the elements' name for mc_last_error.
+int check_range(int64_t first, int64_t count, int64_t n, const char* what) {
+    MC_REQUIRE(first >= 0 && count >= 0 && first <= n && count <= n - first, MC_E_INVALID,
+               "%s [%lld, %lld + %lld) outside [0, %lld]", what, (long long)first, (long long)first, (long long)count,
+               (long long)n);
+    return MC_OK;
+}
+
+// count elements of each of the six planes, plane c from src + c * src_stride to
+// dst + c * dst_stride (the host's side is [6][count]), and the synchronisation.
+int copy_planes(const mc_bases* h, uint32_t* dst, int64_t dst_stride, const uint32_t* src, int64_t src_stride,
+                int64_t count, hipMemcpyKind kind) {
+    for (int c = 0; c < kPlanes; ++c)
+        HIP_TRY(hipMemcpyAsync(dst + c * dst_stride, src + c * src_stride, (size_t)count * 4, kind, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+// The last element of a scan (8 bytes at d_src) through pin[slot], behind what is on the stream.
+int read_total(mc_bases* h, const int64_t* d_src, int slot, int64_t* total) {
+    HIP_TRY(hipMemcpyAsync(h->pin + slot, d_src, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::memcpy(total, h->pin + slot, 8);
+    return MC_OK;
+}
+
+// The events or the planes changed: the row tables and the consensus' insertions are stale.
+void invalidate_ins(mc_bases* h) {
+    h->tab_user.valid = h->tab_cons.valid = false;
+    h->have_cons_ins = false;
+}
+
+// The planes changed: so are the sites, the consensus and the row tables (their rows were kept by depth).
+void invalidate_results(mc_bases* h) {
+    h->have_sites = false;
+    h->have_cons = false;
+    invalidate_ins(h);
+}
+
+}  // namespace
 
 extern "C" int mc_bases_create(int device, int32_t n_ref, mc_bases** out) {
     MC_REQUIRE(out, MC_E_INVALID, "null argument");
@@ -1076,8 +1001,7 @@ int ins_reserve_events(mc_bases* h, size_t need) {
 // with events costs one more for its fill pass.
 int ins_extract(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span) {
     hipStream_t st = h->stream;
-    h->tab_user.valid = h->tab_cons.valid = false;
-    h->have_cons_ins = false;
+    invalidate_ins(h);
     HIP_TRY(h->ins_counts.reserve((size_t)nt));
     HIP_TRY(h->ins_base.reserve((size_t)nt + 1));
     HIP_TRY(hipEventRecord(h->iev[0], st));
@@ -1085,13 +1009,11 @@ int ins_extract(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t 
                        h->order.p + first, max_span, h->ins_counts.p, (const int64_t*)nullptr, (InsEvent*)nullptr,
                        (int64_t)0, (int32_t*)nullptr);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->ins_counts.p, nt, h->ins_base.p,
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->ins_counts.p, nt, h->ins_base.p,
                        (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->pin + 4, h->ins_base.p + nt, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     int64_t total = 0;
-    std::memcpy(&total, h->pin + 4, 8);
+    if (int rc = read_total(h, h->ins_base.p + nt, 4, &total)) return rc;
     MC_REQUIRE(total >= 0, MC_E_STATE, "insertion event count %lld out of range", (long long)total);
     MC_REQUIRE(h->n_events + total <= kMaxEvents, MC_E_RANGE, "more than 2^31 - 1 insertion events");
     if (total) {
@@ -1121,7 +1043,7 @@ int ins_sort(mc_bases* h) {
     HIP_TRY(h->ins_bbase.reserve((size_t)T + 1));
     HIP_TRY(h->ins_cursor.reserve((size_t)T));
     HIP_TRY(h->ins_sorted.reserve((size_t)E));
-    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->tile_total.p, T, h->ins_bbase.p,
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->tile_total.p, T, h->ins_bbase.p,
                        (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
     HIP_TRY(hipGetLastError());
     if (E && T) {
@@ -1154,13 +1076,11 @@ int ins_encode(mc_bases* h, const SiteArgs& sa, InsTable& tab) {
                            (uint32_t*)nullptr);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, tab.rowcount.p, T, tab.rowbase.p,
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, tab.rowcount.p, T, tab.rowbase.p,
                        h->seg_tile.p, S, tab.first.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->pin + 4, tab.rowbase.p + T, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     int64_t total = 0;
-    std::memcpy(&total, h->pin + 4, 8);
+    if (int rc = read_total(h, tab.rowbase.p + T, 4, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= h->n_events, MC_E_STATE, "insertion row count %lld out of range",
                (long long)total);
     HIP_TRY(tab.i.reserve((size_t)total));
@@ -1183,6 +1103,17 @@ int ins_encode(mc_bases* h, const SiteArgs& sa, InsTable& tab) {
 
 namespace {
 
+// ends[0..3] = the first and the last read's (tid, pos): the few words of a
+// device batch the host needs (tile range, order across batches).
+__global__ void bases_ends_kernel(Batch b, int32_t* __restrict__ ends) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        ends[0] = b.tid[0];
+        ends[1] = b.pos[0];
+        ends[2] = b.tid[b.n - 1];
+        ends[3] = b.pos[b.n - 1];
+    }
+}
+
 // The pileup launch of a batch over tiles [first, first + nt) of the sorted
 // order; flag: the reads' flags in device memory on a handle that tracks strand.
 void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span, const uint16_t* flag) {
@@ -1195,26 +1126,119 @@ void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32
                            h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride);
 }
 
+// What every batch entry point checks before it looks at the reads.  flags_fn:
+// the entry point to name to a strand handle's caller who gave no flags;
+// arrays: the per-read arrays other than flag are there.
+int check_batch(const mc_bases* h, int64_t n, bool arrays, bool flagged, const uint16_t* flag, const char* flags_fn) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
+    MC_REQUIRE(flagged || !h->strand, MC_E_STATE, "the handle tracks strand: the reads' flags are needed (%s)",
+               flags_fn);
+    MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
+    MC_REQUIRE(n == 0 || (arrays && (flag || !h->strand)), MC_E_INVALID, "null read arrays");
+    return MC_OK;
+}
+
+int check_arenas(int64_t n_words, const uint32_t* cigar, int64_t seq_bytes, const uint8_t* seq, int64_t qual_bytes,
+                 const uint8_t* qual) {
+    MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
+    MC_REQUIRE((n_words == 0 || cigar) && (seq_bytes == 0 || seq) && (qual_bytes == 0 || qual), MC_E_INVALID,
+               "null arena");
+    return MC_OK;
+}
+
+// The batch's first read does not sort before the previous batch's last one (a
+// first read the pre-pass will reject is left to it).
+int check_order(const mc_bases* h, int32_t tid0, int32_t pos0) {
+    if (h->have_last && tid0 >= 0 && pos0 >= 0)
+        MC_REQUIRE(h->last_tid < tid0 || (h->last_tid == tid0 && h->last_pos <= pos0), MC_E_INVALID,
+                   "read 0: reads are not sorted by (tid, pos) against the previous batch");
+    return MC_OK;
+}
+
+// A batch from the pre-pass on; b: its arrays in device memory (span has room
+// for its reads), flag: its flags there on a handle that tracks strand.
+// host_ends: the first and the last read's (tid, pos) where the host has them,
+// else null and bases_ends_kernel fetches them into flags[2..3] (the handle's
+// flags buffer has room for 256 words), one copy back with the pre-pass' words.
+// The order against the previous batch is checked before the pre-pass' verdict.
+// A read the pre-pass rejected: MC_E_INVALID with its index in *bad_read (else
+// -1) and the message left to the caller, who knows where the arrays are.
+int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const uint16_t* flag, int64_t* bad_read) {
+    *bad_read = -1;
+    hipStream_t st = h->stream;
+    h->pin[0] = kNoBad;
+    h->pin[1] = 0;
+    HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
+    const int64_t groups = (b.n + kThreads - 1) / kThreads;
+    MC_REQUIRE(groups < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^39 reads in one batch");
+    HIP_TRY(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(bases_prepass_kernel, dim3((unsigned)groups), dim3(kThreads), 0, st, b, h->n_ref, h->span.p,
+                       h->flags.p, reinterpret_cast<int32_t*>(h->flags.p + 1));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (!host_ends) {
+        hipLaunchKernelGGL(bases_ends_kernel, dim3(1), dim3(64), 0, st, b, reinterpret_cast<int32_t*>(h->flags.p + 2));
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(h->pin, h->flags.p, host_ends ? 16 : 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int32_t ends[4];
+    std::memcpy(ends, host_ends ? (const void*)host_ends : (const void*)&h->pin[2], 16);
+    if (int rc = check_order(h, ends[0], ends[1])) return rc;
+    const unsigned long long bad = h->pin[0];
+    if (bad != kNoBad) {
+        if (bad < (unsigned long long)b.n)
+            *bad_read = (int64_t)bad;
+        else
+            mc::set_error("read index %llu out of range", bad);
+        return MC_E_INVALID;
+    }
+    int32_t max_span = 0;
+    std::memcpy(&max_span, &h->pin[1], 4);
+    MC_REQUIRE(max_span >= 0, MC_E_STATE, "maximum span %d out of range", max_span);
+    HIP_TRY(hipEventRecord(h->ev[2], st));
+    // A tile the batch can reach starts after (first read's pos - kTile) and before (last read's pos +
+    // max span), in (tid, rel) order: only that range of the sorted tiles is launched.
+    const auto t_lo = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
+                                       std::make_pair(ends[0], (int64_t)ends[1] - kTile));
+    const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
+                                       std::make_pair(ends[2], (int64_t)ends[3] + max_span));
+    if (max_span > 0 && t_lo < t_hi) {
+        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, flag);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->ev[3], st));
+    if (h->tracking && max_span > 0 && t_lo < t_hi) {
+        const int rc = ins_extract(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span);
+        if (rc != MC_OK) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays and the handle's batch buffers are free again
+    float a = 0, c = 0;
+    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+    h->ms_prepass += a;
+    h->ms_pileup += c;
+    h->have_last = true;
+    h->last_tid = ends[2];
+    h->last_pos = ends[3];
+    h->n_reads += b.n;
+    invalidate_results(h);
+    return MC_OK;
+}
+
 // mc_bases_add_batch (flagged false) and mc_bases_add_batch_flags (true).
 int add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos, const int64_t* cig_off,
               const uint32_t* cigar, const int32_t* l_seq, const int64_t* seq_off, const uint8_t* seq,
               const int64_t* qual_off, const uint8_t* qual, bool flagged, const uint16_t* flag) {
-    MC_REQUIRE(h, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
-    MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
-    MC_REQUIRE(flagged || !h->strand, MC_E_STATE,
-               "the handle tracks strand: the reads' flags are needed (mc_bases_add_batch_flags)");
-    MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
+    if (int rc = check_batch(h, n, tid && pos && cig_off && l_seq && seq_off && qual_off, flagged, flag,
+                             "mc_bases_add_batch_flags"))
+        return rc;
     if (n == 0) return MC_OK;
-    MC_REQUIRE(tid && pos && cig_off && l_seq && seq_off && qual_off && (flag || !h->strand), MC_E_INVALID,
-               "null read arrays");
     const int64_t n_words = cig_off[n], seq_bytes = seq_off[n], qual_bytes = qual_off[n];
-    MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
-    MC_REQUIRE((n_words == 0 || cigar) && (seq_bytes == 0 || seq) && (qual_bytes == 0 || qual), MC_E_INVALID,
-               "null arena");
-    if (h->have_last && tid[0] >= 0 && pos[0] >= 0)
-        MC_REQUIRE(h->last_tid < tid[0] || (h->last_tid == tid[0] && h->last_pos <= pos[0]), MC_E_INVALID,
-                   "read 0: reads are not sorted by (tid, pos) against the previous batch");
+    if (int rc = check_arenas(n_words, cigar, seq_bytes, seq, qual_bytes, qual)) return rc;
+    if (int rc = check_order(h, tid[0], pos[0])) return rc;     // (before the upload)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->tid.reserve((size_t)n));
     HIP_TRY(h->pos.reserve((size_t)n));
@@ -1241,63 +1265,14 @@ int add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos, co
     HIP_TRY(up(h->seq.p, seq, (size_t)seq_bytes));
     HIP_TRY(up(h->qual.p, qual, (size_t)qual_bytes));
     if (h->strand) HIP_TRY(up(h->rflag.p, flag, (size_t)n * 2));
-    h->pin[0] = kNoBad;
-    h->pin[1] = 0;
-    HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
-    Batch b{h->tid.p, h->pos.p, h->l_seq.p, h->cig_off.p, h->cigar.p, h->seq_off.p, h->seq.p,
-            h->qual_off.p, h->qual.p, n, n_words, seq_bytes, qual_bytes};
-    const int64_t groups = (n + kThreads - 1) / kThreads;
-    MC_REQUIRE(groups < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^39 reads in one batch");
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(bases_prepass_kernel, dim3((unsigned)groups), dim3(kThreads), 0, st, b, h->n_ref, h->span.p,
-                       h->flags.p, reinterpret_cast<int32_t*>(h->flags.p + 1));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], st));
-    HIP_TRY(hipMemcpyAsync(h->pin, h->flags.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const unsigned long long bad = h->pin[0];
-    if (bad != kNoBad) {
-        if (bad < (unsigned long long)n)
-            name_bad_read(h, (int64_t)bad, tid, pos, cig_off, cigar, l_seq, seq_off, qual_off, n_words, seq_bytes,
-                          qual_bytes);
-        else
-            mc::set_error("read index %llu out of range", bad);
-        return MC_E_INVALID;
-    }
-    int32_t max_span = 0;
-    std::memcpy(&max_span, &h->pin[1], 4);
-    MC_REQUIRE(max_span >= 0, MC_E_STATE, "maximum span %d out of range", max_span);
-    HIP_TRY(hipEventRecord(h->ev[2], st));
-    // A tile the batch can reach starts after (first read's pos - kTile) and before (last read's pos +
-    // max span), in (tid, rel) order: only that range of the sorted tiles is launched.
-    const auto t_lo = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
-                                       std::make_pair(tid[0], (int64_t)pos[0] - kTile));
-    const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
-                                       std::make_pair(tid[n - 1], (int64_t)pos[n - 1] + max_span));
-    if (max_span > 0 && t_lo < t_hi) {
-        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, h->rflag.p);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(h->ev[3], st));
-    if (h->tracking && max_span > 0 && t_lo < t_hi) {
-        const int rc = ins_extract(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span);
-        if (rc != MC_OK) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays and the handle's batch buffers are free again
-    float a = 0, c = 0;
-    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
-    h->ms_prepass += a;
-    h->ms_pileup += c;
-    h->have_last = true;
-    h->last_tid = tid[n - 1];
-    h->last_pos = pos[n - 1];
-    h->n_reads += n;
-    h->have_sites = false;
-    h->have_cons = false;
-    h->have_cons_ins = false;
-    h->tab_user.valid = h->tab_cons.valid = false;
-    return MC_OK;
+    const Batch b{h->tid.p, h->pos.p, h->l_seq.p, h->cig_off.p, h->cigar.p, h->seq_off.p, h->seq.p,
+                  h->qual_off.p, h->qual.p, n, n_words, seq_bytes, qual_bytes};
+    const int32_t ends[4] = {tid[0], pos[0], tid[n - 1], pos[n - 1]};
+    int64_t bad = -1;
+    const int rc = finish_batch(h, b, ends, h->rflag.p, &bad);
+    if (bad >= 0)
+        name_bad_read(h, bad, tid, pos, cig_off, cigar, l_seq, seq_off, qual_off, n_words, seq_bytes, qual_bytes);
+    return rc;
 }
 
 }  // namespace
@@ -1318,127 +1293,53 @@ extern "C" int mc_bases_add_batch_flags(mc_bases* h, int64_t n, const int32_t* t
 
 namespace {
 
-// ends[0..3] = the first and the last read's (tid, pos): the few words of a
-// device batch the host needs (tile range, order across batches).
-__global__ void bases_ends_kernel(Batch b, int32_t* __restrict__ ends) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        ends[0] = b.tid[0];
-        ends[1] = b.pos[0];
-        ends[2] = b.tid[b.n - 1];
-        ends[3] = b.pos[b.n - 1];
-    }
-}
-
 // mc_bases_add_batch_device (flagged false) and mc_bases_add_batch_device_flags (true).
 int add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos, const int64_t* d_cig_off,
                      const uint32_t* d_cigar, int64_t n_words, const int32_t* d_l_seq, const int64_t* d_seq_off,
                      const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
                      int64_t qual_bytes, bool flagged, const uint16_t* d_flag) {
-    MC_REQUIRE(h, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
-    MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
-    MC_REQUIRE(flagged || !h->strand, MC_E_STATE,
-               "the handle tracks strand: the reads' flags are needed (mc_bases_add_batch_device_flags)");
-    MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
+    if (int rc = check_batch(h, n, d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off, flagged, d_flag,
+                             "mc_bases_add_batch_device_flags"))
+        return rc;
     if (n == 0) return MC_OK;
-    MC_REQUIRE(d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off && (d_flag || !h->strand),
-               MC_E_INVALID, "null read arrays");
-    MC_REQUIRE(n_words >= 0 && seq_bytes >= 0 && qual_bytes >= 0, MC_E_INVALID, "negative arena size");
-    MC_REQUIRE((n_words == 0 || d_cigar) && (seq_bytes == 0 || d_seq) && (qual_bytes == 0 || d_qual), MC_E_INVALID,
-               "null arena");
+    if (int rc = check_arenas(n_words, d_cigar, seq_bytes, d_seq, qual_bytes, d_qual)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->span.reserve((size_t)n));
+    const Batch b{d_tid, d_pos, d_l_seq, d_cig_off, d_cigar, d_seq_off, d_seq, d_qual_off, d_qual,
+                  n, n_words, seq_bytes, qual_bytes};
+    int64_t bad = -1;
+    const int rc = finish_batch(h, b, nullptr, d_flag, &bad);
+    if (bad < 0) return rc;
+    // the bad read's fields behind its predecessor's key (two-entry arrays: name_bad_read's i - 1 and i)
     hipStream_t st = h->stream;
-    h->pin[0] = kNoBad;
-    h->pin[1] = 0;
-    HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
-    Batch b{d_tid, d_pos, d_l_seq, d_cig_off, d_cigar, d_seq_off, d_seq, d_qual_off, d_qual,
-            n, n_words, seq_bytes, qual_bytes};
-    const int64_t groups = (n + kThreads - 1) / kThreads;
-    MC_REQUIRE(groups < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^39 reads in one batch");
-    HIP_TRY(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(bases_prepass_kernel, dim3((unsigned)groups), dim3(kThreads), 0, st, b, h->n_ref, h->span.p,
-                       h->flags.p, reinterpret_cast<int32_t*>(h->flags.p + 1));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], st));
-    // flags[2..3] (the handle's flags buffer has room for 256 words): the ends, one copy with the flags
-    hipLaunchKernelGGL(bases_ends_kernel, dim3(1), dim3(64), 0, st, b, reinterpret_cast<int32_t*>(h->flags.p + 2));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->pin, h->flags.p, 32, hipMemcpyDeviceToHost, st));
+    const int64_t i = bad, j = i > 0 ? 1 : 0;
+    int32_t t2[2] = {0, 0}, p2[2] = {0, 0}, l2[2] = {0, 0};
+    int64_t c3[3] = {0, 0, 0}, s2[2] = {0, 0}, q2[2] = {0, 0};
+    const auto down = [st](void* d, const void* s, size_t bytes) {
+        return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, st);
+    };
+    HIP_TRY(down(t2, d_tid + i - j, (size_t)(j + 1) * 4));
+    HIP_TRY(down(p2, d_pos + i - j, (size_t)(j + 1) * 4));
+    HIP_TRY(down(l2 + j, d_l_seq + i, 4));
+    HIP_TRY(down(c3 + j, d_cig_off + i, 16));
+    HIP_TRY(down(s2 + j, d_seq_off + i, 8));
+    HIP_TRY(down(q2 + j, d_qual_off + i, 8));
     HIP_TRY(hipStreamSynchronize(st));
-    int32_t ends[4];
-    std::memcpy(ends, &h->pin[2], 16);
-    if (h->have_last && ends[0] >= 0 && ends[1] >= 0)
-        MC_REQUIRE(h->last_tid < ends[0] || (h->last_tid == ends[0] && h->last_pos <= ends[1]), MC_E_INVALID,
-                   "read 0: reads are not sorted by (tid, pos) against the previous batch");
-    const unsigned long long bad = h->pin[0];
-    if (bad != kNoBad) {
-        if (bad >= (unsigned long long)n) {
-            mc::set_error("read index %llu out of range", bad);
-            return MC_E_INVALID;
+    std::vector<uint32_t> words;
+    int64_t local_words = n_words;
+    if (c3[j] >= 0 && c3[j + 1] >= c3[j] && c3[j + 1] <= n_words) {   // the words, rebased to offset 0
+        words.resize((size_t)(c3[j + 1] - c3[j]));
+        if (!words.empty()) {
+            HIP_TRY(down(words.data(), d_cigar + c3[j], words.size() * 4));
+            HIP_TRY(hipStreamSynchronize(st));
         }
-        // the bad read's fields behind its predecessor's key (two-entry arrays: name_bad_read's i - 1 and i)
-        const int64_t i = (int64_t)bad, j = i > 0 ? 1 : 0;
-        int32_t t2[2] = {0, 0}, p2[2] = {0, 0}, l2[2] = {0, 0};
-        int64_t c3[3] = {0, 0, 0}, s2[2] = {0, 0}, q2[2] = {0, 0};
-        const auto down = [st](void* d, const void* s, size_t bytes) {
-            return hipMemcpyAsync(d, s, bytes, hipMemcpyDeviceToHost, st);
-        };
-        HIP_TRY(down(t2, d_tid + i - j, (size_t)(j + 1) * 4));
-        HIP_TRY(down(p2, d_pos + i - j, (size_t)(j + 1) * 4));
-        HIP_TRY(down(l2 + j, d_l_seq + i, 4));
-        HIP_TRY(down(c3 + j, d_cig_off + i, 16));
-        HIP_TRY(down(s2 + j, d_seq_off + i, 8));
-        HIP_TRY(down(q2 + j, d_qual_off + i, 8));
-        HIP_TRY(hipStreamSynchronize(st));
-        std::vector<uint32_t> words;
-        int64_t local_words = n_words;
-        if (c3[j] >= 0 && c3[j + 1] >= c3[j] && c3[j + 1] <= n_words) {   // the words, rebased to offset 0
-            words.resize((size_t)(c3[j + 1] - c3[j]));
-            if (!words.empty()) {
-                HIP_TRY(down(words.data(), d_cigar + c3[j], words.size() * 4));
-                HIP_TRY(hipStreamSynchronize(st));
-            }
-            // (the bases' and qualities' offsets stay absolute: name_bad_read only compares them)
-            c3[j + 1] -= c3[j];
-            c3[j] = 0;
-            local_words = c3[j + 1];
-        }
-        name_bad_read(h, j, t2, p2, c3, words.data(), l2, s2, q2, local_words, seq_bytes, qual_bytes, i);
-        return MC_E_INVALID;
+        // (the bases' and qualities' offsets stay absolute: name_bad_read only compares them)
+        c3[j + 1] -= c3[j];
+        c3[j] = 0;
+        local_words = c3[j + 1];
     }
-    int32_t max_span = 0;
-    std::memcpy(&max_span, &h->pin[1], 4);
-    MC_REQUIRE(max_span >= 0, MC_E_STATE, "maximum span %d out of range", max_span);
-    HIP_TRY(hipEventRecord(h->ev[2], st));
-    const auto t_lo = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
-                                       std::make_pair(ends[0], (int64_t)ends[1] - kTile));
-    const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
-                                       std::make_pair(ends[2], (int64_t)ends[3] + max_span));
-    if (max_span > 0 && t_lo < t_hi) {
-        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, d_flag);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(h->ev[3], st));
-    if (h->tracking && max_span > 0 && t_lo < t_hi) {
-        const int rc = ins_extract(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span);
-        if (rc != MC_OK) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays are free again
-    float a = 0, c = 0;
-    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
-    h->ms_prepass += a;
-    h->ms_pileup += c;
-    h->have_last = true;
-    h->last_tid = ends[2];
-    h->last_pos = ends[3];
-    h->n_reads += n;
-    h->have_sites = false;
-    h->have_cons = false;
-    h->have_cons_ins = false;
-    h->tab_user.valid = h->tab_cons.valid = false;
-    return MC_OK;
+    name_bad_read(h, j, t2, p2, c3, words.data(), l2, s2, q2, local_words, seq_bytes, qual_bytes, i);
+    return MC_E_INVALID;
 }
 
 }  // namespace
@@ -1471,17 +1372,11 @@ extern "C" int mc_bases_seg_off(const mc_bases* h, int64_t* seg_off) {
 extern "C" int mc_bases_get(const mc_bases* h, int64_t first, int64_t count, uint32_t* out) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
-               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
-               (long long)count, (long long)h->N);
+    if (int rc = check_range(first, count, h->N, "positions")) return rc;
     MC_REQUIRE(count == 0 || out, MC_E_INVALID, "null out");
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
-    for (int c = 0; c < kPlanes; ++c)
-        HIP_TRY(hipMemcpyAsync(out + (size_t)c * (size_t)count, h->planes.p + c * h->stride + first, (size_t)count * 4,
-                               hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MC_OK;
+    return copy_planes(h, out, count, h->planes.p + first, h->stride, count, hipMemcpyDeviceToHost);
 }
 
 extern "C" int mc_bases_device(const mc_bases* h, const uint32_t** d_planes, int64_t* stride, int64_t* n) {
@@ -1530,13 +1425,11 @@ int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, in
                                d_ref, h->tiles.p, sa, h->counts.p);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->counts.p, T, h->base.p,
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->counts.p, T, h->base.p,
                        h->seg_tile.p, S, h->site_first.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->pin + 2, h->base.p + T, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     int64_t total = 0;
-    std::memcpy(&total, h->pin + 2, 8);
+    if (int rc = read_total(h, h->base.p + T, 2, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "site count %lld out of range", (long long)total);
     HIP_TRY(h->site_pos.reserve((size_t)total));
     HIP_TRY(h->site_counts.reserve((size_t)total * kPlanes));
@@ -1583,9 +1476,7 @@ extern "C" int mc_bases_sites_get_reverse(const mc_bases* h, int64_t first, int6
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->have_sites && h->have_sites_rev, MC_E_STATE,
                "no strand sites computed (call mc_bases_sites_strand)");
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->n_sites && count <= h->n_sites - first, MC_E_INVALID,
-               "sites [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count,
-               (long long)h->n_sites);
+    if (int rc = check_range(first, count, h->n_sites, "sites")) return rc;
     MC_REQUIRE(count == 0 || rev_counts, MC_E_INVALID, "null out");
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
@@ -1606,17 +1497,11 @@ extern "C" int mc_bases_get_reverse(const mc_bases* h, int64_t first, int64_t co
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
     MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
-               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
-               (long long)count, (long long)h->N);
+    if (int rc = check_range(first, count, h->N, "positions")) return rc;
     MC_REQUIRE(count == 0 || out, MC_E_INVALID, "null out");
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
-    for (int c = 0; c < kPlanes; ++c)
-        HIP_TRY(hipMemcpyAsync(out + (size_t)c * (size_t)count, h->rev.p + c * h->stride + first, (size_t)count * 4,
-                               hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MC_OK;
+    return copy_planes(h, out, count, h->rev.p + first, h->stride, count, hipMemcpyDeviceToHost);
 }
 
 extern "C" int mc_bases_reverse_device(const mc_bases* h, const uint32_t** d_rev, int64_t* stride, int64_t* n) {
@@ -1634,20 +1519,14 @@ extern "C" int mc_bases_set_strand(mc_bases* h, int64_t first, int64_t count, co
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
     MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
-               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
-               (long long)count, (long long)h->N);
+    if (int rc = check_range(first, count, h->N, "positions")) return rc;
     MC_REQUIRE(count == 0 || (total && rev), MC_E_INVALID, "null in");
     for (int64_t k = 0; k < kPlanes * count; ++k)
         MC_REQUIRE(rev[k] <= total[k], MC_E_INVALID, "channel %lld, position %lld: reverse count %u exceeds total %u",
                    (long long)(k / count), (long long)(first + k % count), rev[k], total[k]);
     const int rc = mc_bases_set(h, first, count, total);
     if (rc != MC_OK || count == 0) return rc;
-    for (int c = 0; c < kPlanes; ++c)
-        HIP_TRY(hipMemcpyAsync(h->rev.p + c * h->stride + first, rev + (size_t)c * (size_t)count, (size_t)count * 4,
-                               hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MC_OK;
+    return copy_planes(h, h->rev.p + first, h->stride, rev, count, count, hipMemcpyHostToDevice);
 }
 
 extern "C" int mc_bases_sites_first(const mc_bases* h, int64_t* site_first) {
@@ -1663,9 +1542,7 @@ extern "C" int mc_bases_sites_get(const mc_bases* h, int64_t first, int64_t coun
                                   uint32_t* site_counts) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->have_sites, MC_E_STATE, "no sites computed (call mc_bases_sites)");
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->n_sites && count <= h->n_sites - first, MC_E_INVALID,
-               "sites [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count,
-               (long long)h->n_sites);
+    if (int rc = check_range(first, count, h->n_sites, "sites")) return rc;
     MC_REQUIRE(count == 0 || (site_pos && site_counts), MC_E_INVALID, "null out");
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
@@ -1691,21 +1568,12 @@ extern "C" int mc_bases_timing(const mc_bases* h, float* prepass_ms, float* pile
 extern "C" int mc_bases_set(mc_bases* h, int64_t first, int64_t count, const uint32_t* in) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= h->N && count <= h->N - first, MC_E_INVALID,
-               "positions [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first,
-               (long long)count, (long long)h->N);
+    if (int rc = check_range(first, count, h->N, "positions")) return rc;
     MC_REQUIRE(count == 0 || in, MC_E_INVALID, "null in");
-    h->have_sites = false;
-    h->have_cons = false;
-    h->have_cons_ins = false;
-    h->tab_user.valid = h->tab_cons.valid = false;      // (their rows were kept by depth)
+    invalidate_results(h);
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
-    for (int c = 0; c < kPlanes; ++c)
-        HIP_TRY(hipMemcpyAsync(h->planes.p + c * h->stride + first, in + (size_t)c * (size_t)count, (size_t)count * 4,
-                               hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MC_OK;
+    return copy_planes(h, h->planes.p + first, h->stride, in, count, count, hipMemcpyHostToDevice);
 }
 
 extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t call_ppm,
@@ -1750,10 +1618,8 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
                        h->seg_tile.p, S, h->cons_first.p, h->cons_rows.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(h->cev[2], st));
-    HIP_TRY(hipMemcpyAsync(h->pin + 3, h->cons_pre.p + 7 * (T + 1) + T, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
     int64_t total = 0;
-    std::memcpy(&total, h->pin + 3, 8);
+    if (int rc = read_total(h, h->cons_pre.p + 7 * (T + 1) + T, 3, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "consensus length %lld out of range", (long long)total);
     int64_t inserted = 0;
     if (with_ins) {
@@ -1778,7 +1644,7 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
             HIP_TRY(hipGetLastError());
         }
         for (int c = 0; c < 2; ++c) {
-            hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->cons_ins_cols.p + c * T, T,
+            hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->cons_ins_cols.p + c * T, T,
                                h->cons_ins_pre.p + c * (T + 1), h->seg_tile.p, S, h->cons_ins_first.p + c * (S + 1));
             HIP_TRY(hipGetLastError());
         }
@@ -1787,36 +1653,24 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
                            h->cons_ins_rows.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(h->iev[5], st));
-        HIP_TRY(hipMemcpyAsync(h->pin + 4, h->cons_ins_pre.p + T, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        std::memcpy(&inserted, h->pin + 4, 8);
+        rc = read_total(h, h->cons_ins_pre.p + T, 4, &inserted);
+        if (rc != MC_OK) return rc;
         MC_REQUIRE(inserted >= 0 && inserted <= kMaxInsLen * tb.n, MC_E_STATE, "inserted bases %lld out of range",
                    (long long)inserted);
         HIP_TRY(hipEventElapsedTime(&h->ms_ins_cons, h->iev[4], h->iev[5]));
-        HIP_TRY(h->cons_compact.reserve((size_t)(total + inserted)));
-        HIP_TRY(hipEventRecord(h->cev[3], st));
-        if (T) {
+    }
+    HIP_TRY(h->cons_compact.reserve((size_t)(total + inserted)));
+    HIP_TRY(hipEventRecord(h->cev[3], st));
+    if (T) {
+        if (with_ins) {
+            const InsTable& tb = h->tab_cons;
             hipLaunchKernelGGL(cons_emit_ins_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->cons_aligned.p,
                                h->tiles.p, h->cons_pre.p + 7 * (T + 1), h->cons_ins_pre.p, tb.rowbase.p, tb.i.p,
                                tb.len.p, tb.code.p, h->cons_called.p, h->cons_compact.p, total + inserted);
-            HIP_TRY(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(cons_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->cons_aligned.p,
+                               h->tiles.p, h->cons_pre.p + 7 * (T + 1), h->cons_compact.p);
         }
-        HIP_TRY(hipEventRecord(h->cev[4], st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipEventElapsedTime(&h->ms_cons_call, h->cev[0], h->cev[1]));
-        HIP_TRY(hipEventElapsedTime(&h->ms_cons_scan, h->cev[1], h->cev[2]));
-        HIP_TRY(hipEventElapsedTime(&h->ms_cons_emit, h->cev[3], h->cev[4]));
-        h->n_cons = total + inserted;
-        h->have_cons = true;
-        h->have_cons_ins = true;
-        *n_out = h->n_cons;
-        return MC_OK;
-    }
-    HIP_TRY(h->cons_compact.reserve((size_t)total));
-    HIP_TRY(hipEventRecord(h->cev[3], st));
-    if (T) {
-        hipLaunchKernelGGL(cons_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->cons_aligned.p, h->tiles.p,
-                           h->cons_pre.p + 7 * (T + 1), h->cons_compact.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->cev[4], st));
@@ -1824,9 +1678,10 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
     HIP_TRY(hipEventElapsedTime(&h->ms_cons_call, h->cev[0], h->cev[1]));
     HIP_TRY(hipEventElapsedTime(&h->ms_cons_scan, h->cev[1], h->cev[2]));
     HIP_TRY(hipEventElapsedTime(&h->ms_cons_emit, h->cev[3], h->cev[4]));
-    h->n_cons = total;
+    h->n_cons = total + inserted;
     h->have_cons = true;
-    *n_out = total;
+    h->have_cons_ins = with_ins;
+    *n_out = h->n_cons;
     return MC_OK;
 }
 
@@ -1855,9 +1710,7 @@ extern "C" int mc_bases_consensus_get(const mc_bases* h, int compact, int64_t fi
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->have_cons, MC_E_STATE, "no consensus computed (call mc_bases_consensus)");
     const int64_t n = compact ? h->n_cons : h->N;
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= n && count <= n - first, MC_E_INVALID,
-               "%s letters [%lld, %lld + %lld) outside [0, %lld]", compact ? "compact" : "aligned", (long long)first,
-               (long long)first, (long long)count, (long long)n);
+    if (int rc = check_range(first, count, n, compact ? "compact letters" : "aligned letters")) return rc;
     MC_REQUIRE(count == 0 || letters, MC_E_INVALID, "null out");
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
@@ -1930,9 +1783,7 @@ extern "C" int mc_bases_insertions_get(const mc_bases* h, int64_t first, int64_t
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->tracking && h->tab_user.valid, MC_E_STATE, "no insertions computed (call mc_bases_insertions)");
     const InsTable& t = h->tab_user;
-    MC_REQUIRE(first >= 0 && count >= 0 && first <= t.n && count <= t.n - first, MC_E_INVALID,
-               "rows [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count,
-               (long long)t.n);
+    if (int rc = check_range(first, count, t.n, "rows")) return rc;
     MC_REQUIRE(count == 0 || (i && len && code && other && cnt), MC_E_INVALID, "null out");
     if (count == 0) return MC_OK;
     HIP_TRY(hipSetDevice(h->device));
@@ -1997,8 +1848,7 @@ extern "C" int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const 
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     h->sorted_valid = false;
-    h->tab_user.valid = h->tab_cons.valid = false;
-    h->have_cons_ins = false;
+    invalidate_ins(h);
     h->have_cons = false;
     HIP_TRY(h->ins_sorted.reserve((size_t)n));
     HIP_TRY(h->ins_weight.reserve((size_t)n));
@@ -2008,7 +1858,7 @@ extern "C" int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const 
         HIP_TRY(hipMemcpyAsync(h->ins_weight.p, cnt, (size_t)n * 4, hipMemcpyHostToDevice, st));
     }
     if (T) HIP_TRY(hipMemcpyAsync(h->tile_total.p, total.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sites_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->tile_total.p, T, h->ins_bbase.p,
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->tile_total.p, T, h->ins_bbase.p,
                        (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));

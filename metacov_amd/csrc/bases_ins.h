@@ -1,7 +1,7 @@
 // Insertion alleles: the kernels of the opt-in insertion stage of mc_bases
 // (the contract is the header's, "Insertion alleles").  Included by bases.hip
-// inside its anonymous namespace, behind Tile, Batch, lower_bound and the
-// sites kernels, whose one-workgroup scan every stage here reuses.
+// inside its anonymous namespace, behind Tile, Batch, lower_bound and
+// tile_scan_kernel, the one-workgroup scan every stage here reuses.
 //
 // Launches, all on the handle's stream, none waiting on another workgroup:
 //   ins_extract_kernel<false / true>   per batch, one workgroup per tile of the
@@ -9,7 +9,7 @@
 //                         searches; one THREAD per read (the walk reads CIGAR
 //                         words only, a few per read, so a wave per read would
 //                         idle 63 lanes).  The count pass writes the tile's
-//                         number of events, sites_scan_kernel prefixes them,
+//                         number of events, tile_scan_kernel prefixes them,
 //                         the fill pass appends 24-byte events to the handle's
 //                         table inside the range its count pass sized (slot
 //                         by an LDS counter, checked before every store) and

@@ -32,6 +32,7 @@
 
 #include "../../include/metacov_amd.h"
 #include "common.h"
+#include "tile_util.h"
 
 namespace {
 
@@ -169,16 +170,6 @@ __global__ __launch_bounds__(kThreads) void ecor_kernel(
 }
 
 }  // namespace
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
 
 struct mc_ecor {
     int device = 0;

@@ -40,16 +40,7 @@
 #include "../../include/metacov_amd.h"
 #include "common.h"
 #include "exp_gpu.h"
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
+#include "tile_util.h"
 
 #pragma clang fp contract(off)
 

@@ -36,16 +36,19 @@
 
 #include "../../include/metacov_amd.h"
 #include "common.h"
+#include "tile_util.h"
 
 namespace {
+
+using mc::Buf;
+using mc::kScanThreads;
+using mc::kScanWidth;                               // tiles per iteration of pass B
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRounds = 8;                          // int4 loads per lane
 constexpr int kTile = kThreads * 4 * kRounds;       // 8192 positions
 constexpr int kWavePos = kTile / kWaves;            // 2048
-constexpr int kScanThreads = 1024;
-constexpr int kScanWidth = kScanThreads * 4;        // tiles per iteration of pass B
 constexpr int kMaxEdges = 16;
 constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_set_contigs' length bound
 
@@ -153,43 +156,8 @@ __global__ __launch_bounds__(kScanThreads) void runs_scan_kernel(const int32_t* 
                                                                 int64_t n_tiles, int64_t* __restrict__ base,
                                                                 const int64_t* __restrict__ seg_tile, int64_t S,
                                                                 int64_t* __restrict__ seg_first) {
-    __shared__ int32_t wsum[kScanThreads / 64];
-    __shared__ int64_t carry_s;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (int64_t i0 = 0; i0 < n_tiles; i0 += kScanWidth) {
-        const int64_t i = i0 + 4 * (int64_t)t;
-        int32_t c[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c[k] = i + k < n_tiles ? counts[i + k] : 0;
-        const int32_t mine = c[0] + c[1] + c[2] + c[3];     // <= 4 kTile; an iteration's sum < 2^27
-        int32_t inc = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int32_t o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int32_t wbase = 0, total = 0;
-        for (int w = 0; w < kScanThreads / 64; ++w) {
-            if (w < wave) wbase += wsum[w];
-            total += wsum[w];
-        }
-        int64_t b = carry_s + wbase + (inc - mine);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (i + k < n_tiles) base[i + k] = b;
-            b += c[k];
-        }
-        __syncthreads();                                    // every thread has read carry_s and wsum
-        if (t == 0) carry_s += total;
-        __syncthreads();
-    }
-    if (t == 0) base[n_tiles] = carry_s;
-    __syncthreads();                                        // base[] is visible to this workgroup
-    for (int64_t s = t; s <= S; s += kScanThreads) seg_first[s] = base[seg_tile[s]];
+    mc::tile_scan(counts, n_tiles, base);
+    for (int64_t s = threadIdx.x; s <= S; s += kScanThreads) seg_first[s] = base[seg_tile[s]];
 }
 
 template <bool Q>
@@ -237,40 +205,6 @@ __global__ __launch_bounds__(kThreads) void runs_emit_kernel(const int32_t* __re
         }
     }
 }
-
-}  // namespace
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
-
-namespace {
-
-// grow-only device array
-template <typename T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(n, (size_t)256);
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
 
 }  // namespace
 

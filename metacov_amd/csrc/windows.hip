@@ -46,8 +46,11 @@
 
 #include "../../include/metacov_amd.h"
 #include "common.h"
+#include "tile_util.h"
 
 namespace {
+
+using mc::Buf;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -440,37 +443,7 @@ __global__ __launch_bounds__(kThreads) void windows_hist_kernel(const int32_t* _
 
 }  // namespace
 
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
-
 namespace {
-
-// grow-only device array
-template <typename T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(n, (size_t)256);
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
 
 struct Contig {
     int32_t tid = 0;

@@ -1,7 +1,9 @@
 """Per-position base counts on the GPU (csrc/bases.hip) against the model in
 tests/bases_model.py: exact equality of seg_off, the six planes and the sites.
 Shapes are a few tiles at most; P (tile positions) comes from the library."""
+import ctypes
 import os
+import re
 
 import numpy as np
 import pytest
@@ -268,6 +270,76 @@ def test_invalid_batches(bc):
     expect(r, "read 299: reference span")
 
 
+def test_invalid_batches_device(bc):
+    """test_invalid_batches' batches through mc_bases_add_batch_device, the
+    arrays uploaded with torch: code and message are the host entry point's,
+    the planes stay zero and the handle takes the good batch afterwards.  Then
+    a batch that starts before the previous one ended, on both paths: that
+    message comes before the verdict on a bad read further in."""
+    import torch
+    lib = bc._lib
+    rng = np.random.default_rng(7)
+    good = [read(rng, 0, 10 * k, "12M") for k in range(300)]
+    tids, starts, ends = np.array([0]), np.array([0]), np.array([3100])
+    gb = bm.make_batch(good)
+    _, want = bm.counts_model([gb], tids, starts, ends, 0)
+
+    def host(b):
+        rc = lib.mc_bases_add_batch(bc._h, bm.n_reads(b), *[_lib.ptr(a) for a in bm.batch_args(b)])
+        return rc, lib.mc_last_error().decode() if rc else ""
+
+    def device(b):
+        arrs = bm.batch_args(b)
+        dev = [torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda() for a in arrs]
+        torch.cuda.synchronize()
+        tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual = [ctypes.c_void_p(t.data_ptr()) for t in dev]
+        rc = lib.mc_bases_add_batch_device(bc._h, bm.n_reads(b), tid, pos, cig_off, cigar, len(b["cigar"]), l_seq,
+                                           seq_off, seq, len(b["seq"]), qual_off, qual, len(b["qual"]))
+        return rc, lib.mc_last_error().decode() if rc else ""
+
+    def expect(reads, match, **kw):
+        b = bm.make_batch(reads, **kw)
+        bc.begin(tids, starts, ends)
+        rc, msg = host(b)
+        assert rc == _lib.MC_E_INVALID and re.search(match, msg), msg
+        bc.begin(tids, starts, ends)
+        assert device(b) == (rc, msg)
+        assert bc.counts().sum() == 0                             # the batch added nothing
+        assert device(gb) == (_lib.MC_OK, "")                     # and the handle is usable
+        assert np.array_equal(bc.counts(), want)
+
+    r = list(good)
+    r[200], r[201] = r[201], r[200]
+    expect(r, "^read 201: .*not sorted")
+    r = list(good)
+    r[259] = (N_REF,) + r[259][1:]
+    expect(r[:260], "^read 259: tid %d out of range" % N_REF)
+    r = list(good)
+    r[0] = (-1,) + r[0][1:]
+    expect(r, "^read 0: tid -1 out of range")
+    r = list(good)
+    r[0] = (0, -5) + r[0][2:]
+    expect(r, "^read 0: negative pos")
+    ls = [12] * 300
+    ls[77], ls[130] = 11, 13
+    expect(good, "^read 77: CIGAR query length 12 differs from l_seq 11", l_seq=ls)
+    r = list(good)
+    r[299] = (0, 2990, "".join(["1M%dN" % ((1 << 28) - 1)] * 8) + "4M", r[299][3], 30)
+    expect(r, "^read 299: reference span")
+    # the previous batch ended at 2990
+    early = bm.make_batch([(0, 2989, "1M", "A", 30), (0, 2995, "1M", "A", 30), (0, 2994, "1M", "A", 30)])
+    seen = []
+    for add in (host, device):
+        bc.begin(tids, starts, ends)
+        assert add(gb) == (_lib.MC_OK, "")
+        seen.append(add(early))
+        assert np.array_equal(bc.counts(), want)
+        assert add(bm.slice_batch(early, 1, 2)) == (_lib.MC_OK, "")          # 2995 alone follows 2990
+        assert bc.counts().sum() == want.sum() + 1
+    assert seen[0] == seen[1] == (_lib.MC_E_INVALID,
+                                  "read 0: reads are not sorted by (tid, pos) against the previous batch")
+
+
 def test_calls_out_of_order(lib_built):
     with mb.BaseCounter(2, 0) as h:
         b = bm.make_batch([(0, 0, "1M", "A", 30)])
@@ -366,6 +438,34 @@ def test_sites_tiles_and_segments(bc, P):
     ref = rng.integers(0, 5, size=planes.shape[1]).astype(np.uint8)
     check_sites(bc, planes, starts, (1, 1, 0), ref)
     check_sites(bc, planes, starts, (2, 2, 250000), ref)
+
+
+def test_sites_many_one_position_segments(bc):
+    """5000 segments of one position each: more tiles than one scan iteration
+    (4096).  The tiles on both sides of that edge are sites, are none, and are
+    mixed; thresholds that keep no position and every position besides."""
+    rng = np.random.default_rng(21)
+    S, edge = 5000, slice(4094, 4098)
+    segs = [(int(rng.integers(0, N_REF)), i, i + 1) for i in rng.integers(0, 10 ** 6, size=S).tolist()]
+    tids, starts, ends = (np.array(x, np.int64) for x in zip(*segs))
+    assert bc.begin(tids, starts, ends) == S
+    assert bc.timing()["tiles"] == S
+    args = (10, 3, 100000)
+    col = {1: (30, 9, 0, 0, 2, 0),           # C: 9 of 39 beside the base allele A
+           0: (30, 2, 0, 0, 9, 0)}           # C: 2 < min_count; N is no allele
+    ref = rng.integers(0, 5, size=S).astype(np.uint8)
+    ref[edge] = [0, 4, 0, 4]                 # A, or unknown: the major allele A
+    for pattern in ((1, 1, 1, 1), (0, 0, 0, 0), (1, 0, 0, 1), (0, 1, 1, 0)):
+        planes = rng.integers(0, 25, size=(6, S)).astype(np.uint32)
+        planes[:, rng.random(S) < 0.2] = 0
+        planes[:, edge] = np.array([col[k] for k in pattern], np.uint32).T
+        bc.set_counts(0, planes)
+        for r in (None, ref):
+            got = check_sites(bc, planes, starts, args, r)
+            assert 0 < len(got) < S
+            assert np.diff(got.first)[edge].tolist() == list(pattern)
+        assert len(check_sites(bc, planes, starts, (1 << 40, 0, 0))) == 0
+        assert len(check_sites(bc, planes, starts, (0, 0, 0), ref)) == S
 
 
 # ------------------------------------------------------------ the int32 edge

@@ -297,6 +297,44 @@ def test_sites_on_crafted_planes(bc, P):
     assert len(got) == total.shape[1] and np.array_equal(got.rev_counts, rev.T) and np.array_equal(got.counts, total.T)
 
 
+def test_sites_many_one_position_segments(bc):
+    """5000 segments of one position each on a strand handle: more tiles than
+    one scan iteration (4096), the tiles around that edge sites on both
+    strands, on one, and too weak on one."""
+    rng = np.random.default_rng(22)
+    S, edge = 5000, slice(4094, 4098)
+    segs = [(int(rng.integers(0, N_REF)), i, i + 1) for i in rng.integers(0, 10 ** 6, size=S).tolist()]
+    tids, starts, ends = arrays(segs)
+    total = rng.integers(0, 25, size=(6, S)).astype(np.uint32)
+    total[:, rng.random(S) < 0.2] = 0
+    rev = (total * rng.random((6, S))).astype(np.uint32)
+    total[:, edge] = np.array([(30, 9, 0, 0, 2, 0)] * 4, np.uint32).T          # C: 9 of 39 beside the base allele A
+    rev[:, edge] = np.array([(15, 4, 0, 0, 1, 0), (15, 2, 0, 0, 1, 0),         # C: 5 + 4, 7 + 2,
+                             (15, 9, 0, 0, 1, 0), (15, 1, 0, 0, 1, 0)], np.uint32).T   # 0 + 9 and 8 + 1
+    assert (rev <= total).all()
+    ref = rng.integers(0, 5, size=S).astype(np.uint8)
+    ref[edge] = [0, 4, 0, 4]
+    args = (10, 3, 100000)
+    assert bc.begin(tids, starts, ends, strand=True) == S
+    bc.set_counts(0, total, rev=rev)
+    assert bc.timing()["tiles"] == S
+    off = bc.seg_off
+    with mb.BaseCounter(N_REF, 0) as plain:
+        plain.begin(tids, starts, ends)
+        plain.set_counts(0, total)
+        for K, pattern in ((0, [1, 1, 1, 1]), (2, [1, 1, 0, 0])):
+            for r in (None, ref):
+                got = bc.sites(*args, ref=r, min_alt_strand=K)
+                first, pos, cnt, rc = sm.sites_model(total, rev, off, starts, *args, K, r)
+                assert np.array_equal(got.first, first) and np.array_equal(got.pos, pos), (K, r is not None)
+                assert np.array_equal(got.counts, cnt) and np.array_equal(got.rev_counts, rc)
+                assert 0 < len(got) < S and np.diff(got.first)[edge].tolist() == pattern
+                if K == 0:
+                    want = plain.sites(*args, ref=r)
+                    assert np.array_equal(got.first, want.first) and np.array_equal(got.pos, want.pos)
+                    assert np.array_equal(got.counts, want.counts)
+
+
 def _plane_index(sites, off, starts):
     """Plane indices of the sites."""
     out = np.zeros(len(sites), np.int64)
