@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "npstd.h"
 #include "capmask.h"
+#include "tile_util.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -31,16 +32,6 @@ using namespace mc;
 #define MC_PLAIN_TILES_PER_CHUNK 4
 #endif
 constexpr int kPlainTilesPerChunk = MC_PLAIN_TILES_PER_CHUNK;   // plain K2, short reads
-
-#define HIP_TRY(expr)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess) {                                                \
-            mc::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                          __FILE__, __LINE__);                                 \
-            return MC_E_HIP;                                                   \
-        }                                                                      \
-    } while (0)
 
 namespace {
 
@@ -612,20 +603,10 @@ extern "C" int mc_clear_reads(mc_ctx* ctx) {
     return MC_OK;
 }
 
-// MC_STEP_EVENTS 0: a fused call records no timing events (A/B of their
-// cost only: its kernel times then read 0)
-#ifndef MC_STEP_EVENTS
-#define MC_STEP_EVENTS 1
-#endif
-// MC_EXT_EVENTS 1: a fused call's timing events ride on its launches
-// (hipExtLaunchKernel's start / stop events) instead of four hipEventRecord
-// calls (the one before the probe sits between a call's entry and its first
-// launch).  Back-to-back calls ran slower that way: C2 0.0821 -> 0.0870 ms,
-// C3 1.0549 -> 1.0588, one N = 8 share 0.1827 -> 0.1858
-// (profiles/r06/r06w_ab_*).
-#ifndef MC_EXT_EVENTS
-#define MC_EXT_EVENTS 0
-#endif
+// A fused call's timing events are four hipEventRecord calls around its
+// launches.  Riding on the launches instead (hipExtLaunchKernel's start /
+// stop events), back-to-back calls ran slower: C2 0.0821 -> 0.0870 ms, C3
+// 1.0549 -> 1.0588, one N = 8 share 0.1827 -> 0.1858 (profiles/r06/r06w_ab_*).
 static float elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
@@ -868,8 +849,7 @@ extern "C" int mc_prepare(mc_ctx* ctx) {
         hipLaunchKernelGGL(long_scan_final_kernel, dim3(bt + bc), dim3(kBlock), 0, s, A);
         HIP_TRY(hipGetLastError());
         if (counted && end_words) {
-            // its own resident grid (the LDS event buffer of MC_FILL_SORTED
-            // lowers its occupancy); counts and fill need not share sub-ranges
+            // its own resident grid; counts and fill need not share sub-ranges
             const int64_t nbw = std::max<int64_t>(1, std::min<int64_t>(subs, ctx->long_grid_words));
             const int64_t perw = (subs + nbw - 1) / nbw * kLongSub;
             hipLaunchKernelGGL(long_fill_words_kernel, dim3((unsigned)nbw), dim3(kBlock), 0, s, ctx->d_endw.p, n,
@@ -986,7 +966,7 @@ static int prepare_direct(mc_ctx* ctx) {
     if (int rc = run_k1(ctx)) return rc;
     // the prepare's span: this event to K2's start event (probe + window)
     auto& T = ctx->ts[ctx->ts_cur];
-    if (MC_STEP_EVENTS && !MC_EXT_EVENTS) HIP_TRY(hipEventRecord(T.e[0], s));
+    HIP_TRY(hipEventRecord(T.e[0], s));
     T.prep = true;
     ctx->ring = kRing;
     ctx->short_max = ctx->ring - kTileW;
@@ -1011,7 +991,7 @@ static int prepare_direct(mc_ctx* ctx) {
                 ctx->d_dres.p, ++ctx->direct_gen};
     const int64_t M = (n + kProbeStride - 1) >> kProbeShift;
     hipExtLaunchKernelGGL(probe_kernel, dim3((unsigned)std::max<int64_t>(1, (M + kBlock - 1) / kBlock)),
-                          dim3(kBlock), 0, s, MC_STEP_EVENTS && MC_EXT_EVENTS ? T.e[0] : nullptr, nullptr, 0, P);
+                          dim3(kBlock), 0, s, nullptr, nullptr, 0, P);
     HIP_TRY(hipGetLastError());
     HIP_TRY(ctx->d_depth.reserve((size_t)(ctx->n_chunks * ctx->chunk_w)));
     ctx->has_long = false;
@@ -1095,11 +1075,8 @@ extern "C" int mc_set_direct_prepare(mc_ctx* ctx, int enable) {
     return MC_OK;
 }
 
-// Resident workgroups of a K2 variant (queried once per ctx and LDS size),
-// at most MC_K2_PER_CU per CU (0: as many as fit).
-#ifndef MC_K2_PER_CU
-#define MC_K2_PER_CU 0
-#endif
+// Resident workgroups of a K2 variant (queried once per ctx and LDS size):
+// as many as fit.
 static int occupancy_grid(mc_ctx* ctx, int variant, const void* kernel, size_t lds, int64_t work,
                           int* grid) {
     int& cached = ctx->k2_resident[variant];
@@ -1108,7 +1085,6 @@ static int occupancy_grid(mc_ctx* ctx, int variant, const void* kernel, size_t l
         HIP_TRY(hipGetDevice(&dev));
         HIP_TRY(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, kK2Block, lds));
-        if (MC_K2_PER_CU > 0) per = std::min(per, (int)MC_K2_PER_CU);
         cached = ncu * std::max(1, per);
         ctx->k2_resident_lds[variant] = lds;
     }
@@ -1118,17 +1094,14 @@ static int occupancy_grid(mc_ctx* ctx, int variant, const void* kernel, size_t l
 
 // Chunk geometry of a K2 launch.  The plain K2 runs on the index's base
 // chunks unless long reads need full ones (their end buckets and carries are
-// per full chunk).  MC_FUSED_BASE_CHUNKS: the fused K2 too.
-#ifndef MC_FUSED_BASE_CHUNKS
-#define MC_FUSED_BASE_CHUNKS 0
-#endif
+// per full chunk).  The fused K2 always runs on full chunks.
 struct K2Geom {
     int tpc;
     int64_t n_chunks, chunk_w;
     int cstride;
 };
 static K2Geom k2_geom(const mc_ctx* ctx, bool stats) {
-    const bool full = ctx->has_long || (stats && !MC_FUSED_BASE_CHUNKS);
+    const bool full = ctx->has_long || stats;
     if (full) return {ctx->tiles_per_chunk, ctx->n_chunks, ctx->chunk_w, ctx->cstride};
     return {ctx->tpc_base, ctx->n_chunks_base, (int64_t)ctx->tpc_base * kTileW, 1};
 }
@@ -1189,28 +1162,27 @@ static int launch_depth(mc_ctx* ctx, const FusedRegions& fr, hipEvent_t ea = nul
                                        : 0)) * 4;
     const bool lng = ctx->has_long;
     const bool dir = ctx->direct;
-    const void* kfn = stats ? (lng ? (const void*)depth_kernel<true, true, false>
-                                   : dir ? (const void*)depth_kernel<true, false, true>
-                                         : (const void*)depth_kernel<true, false, false>)
-                            : (lng ? (const void*)depth_kernel<false, true, false>
-                                   : dir ? (const void*)depth_kernel<false, false, true>
-                                         : (const void*)depth_kernel<false, false, false>);
+    // the six variants share one signature: the occupancy query and the
+    // launch both go through this pointer
+    using K2Fn = decltype(&depth_kernel<true, true, false>);
+    const K2Fn variants[2][3] = {
+        {depth_kernel<true, true, false>, depth_kernel<true, false, true>, depth_kernel<true, false, false>},
+        {depth_kernel<false, true, false>, depth_kernel<false, false, true>, depth_kernel<false, false, false>}};
+    const K2Fn kfn = variants[stats ? 0 : 1][lng ? 0 : dir ? 1 : 2];
     const K2Geom geo = k2_geom(ctx, stats);
     const int tpc = geo.tpc;
     const int64_t nch = geo.n_chunks;
     const int cstride = geo.cstride;
     const int64_t* cfirst = ctx->d_chunk_first.p;
     int grid = 0;
-    if (int rc = occupancy_grid(ctx, (stats ? 1 : 0) + (lng ? 2 : dir ? 4 : 0), kfn, lds, nch, &grid))
+    if (int rc = occupancy_grid(ctx, (stats ? 1 : 0) + (lng ? 2 : dir ? 4 : 0), (const void*)kfn, lds, nch, &grid))
         return rc;
     if (!stats) {   // the fused path's fused_init_kernel (or the last K3b) zeroes them
         ctx->fused_clean = false;   // this K2 consumes the queue
         HIP_TRY(hipMemsetAsync(ctx->d_queue.p, 0, 32, s));
         HIP_TRY(hipMemsetAsync(ctx->d_maxdepth.p, 0, 16, s));
     }
-    hipEvent_t k2_start = MC_STEP_EVENTS || !ea ? (ea ? ea : ctx->ev[4]) : nullptr;
-    hipEvent_t k2_stop = MC_STEP_EVENTS || !eb ? (eb ? eb : ctx->ev[5]) : nullptr;
-    if (!MC_EXT_EVENTS && k2_start) HIP_TRY(hipEventRecord(k2_start, s));
+    HIP_TRY(hipEventRecord(ea ? ea : ctx->ev[4], s));
     const int64_t* toff = ctx->has_long ? ctx->d_tile_off.p : nullptr;
     const int32_t* tev = ctx->has_long ? ctx->d_tile_ev.p : nullptr;
     const int* ccar = ctx->has_long ? ctx->d_chunk_carry.p : nullptr;
@@ -1231,25 +1203,12 @@ static int launch_depth(mc_ctx* ctx, const FusedRegions& fr, hipEvent_t ea = nul
     const K2Consts* dk = nullptr;
     if (int rc = k2_consts(ctx, kc, &dk)) return rc;
     const int win_parity = (int)(ctx->direct_gen & 1);
-#define MC_LAUNCH_K2(S, L, D)                                                                  \
-    hipExtLaunchKernelGGL((depth_kernel<S, L, D>), dim3(grid), dim3(kK2Block), (uint32_t)lds, s,        \
-                          MC_EXT_EVENTS ? k2_start : nullptr, MC_EXT_EVENTS ? k2_stop : nullptr, 0u, kc.A, dk, \
-                       ctx->n_reads, ctx->d_coff.p,                                               \
-                       cfirst, cstride, nch, tpc, ctx->short_max,                                \
-                       toff, tev, ccar, ctx->d_depth.p, ctx->d_queue.p, ctx->d_maxdepth.p,        \
-                       (unsigned long long)ctx->direct_gen, win_parity)
-    if (stats) {
-        if (lng) MC_LAUNCH_K2(true, true, false);
-        else if (dir) MC_LAUNCH_K2(true, false, true);
-        else MC_LAUNCH_K2(true, false, false);
-    } else {
-        if (lng) MC_LAUNCH_K2(false, true, false);
-        else if (dir) MC_LAUNCH_K2(false, false, true);
-        else MC_LAUNCH_K2(false, false, false);
-    }
-#undef MC_LAUNCH_K2
+    hipExtLaunchKernelGGL(kfn, dim3(grid), dim3(kK2Block), (uint32_t)lds, s, nullptr, nullptr, 0u, kc.A, dk,
+                          ctx->n_reads, ctx->d_coff.p, cfirst, cstride, nch, tpc, ctx->short_max,
+                          toff, tev, ccar, ctx->d_depth.p, ctx->d_queue.p, ctx->d_maxdepth.p,
+                          (unsigned long long)ctx->direct_gen, win_parity);
     HIP_TRY(hipGetLastError());
-    if (!MC_EXT_EVENTS && k2_stop) HIP_TRY(hipEventRecord(k2_stop, s));
+    HIP_TRY(hipEventRecord(eb ? eb : ctx->ev[5], s));
     ctx->t_depth = ea == nullptr;   // else the caller's set carries the time
     ctx->t.depth_launches += 1;
     ctx->depth_valid = true;
@@ -1492,27 +1451,9 @@ static int direct_verdict_sync(mc_ctx* ctx) {
     return kRedo;
 }
 
-// The launches of a fused call whose region arrays are staged in
-// ctx->fstage (just now, or by an identical earlier call).
 // Waits until the stream has written stamp `seq` (spinning on mapped host
 // memory; a stream query every ~1k spins reports a failed stream), or, where
 // the stream cannot write stamps, for the stream to drain.
-// How a fused call learns that its last kernel is done (MC_DONE_MODE):
-// 0 a stream write command after it writes the stamp; 1 K3b's last
-// workgroup writes the stamp (grid_done_stamp) when K3b is the call's last
-// kernel, else as 0; 2 the host polls the event recorded after it.
-#ifndef MC_DONE_MODE
-#define MC_DONE_MODE 1
-#endif
-static int wait_event_spin(hipEvent_t ev) {
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) return MC_OK;
-        if (e != hipErrorNotReady) HIP_TRY(e);
-        __builtin_ia32_pause();
-    }
-}
-
 static int wait_stamp(mc_ctx* ctx, unsigned long long seq) {
     if (!ctx->stamp_ok) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1529,6 +1470,11 @@ static int wait_stamp(mc_ctx* ctx, unsigned long long seq) {
     }
 }
 
+// The launches of a fused call whose region arrays are staged in
+// ctx->fstage (just now, or by an identical earlier call).  The call learns
+// that its last kernel is done from a stamp in mapped host memory: K3b's last
+// workgroup writes it (grid_done_stamp) when K3b is the call's last kernel,
+// else a stream write command after the last kernel does.
 static int depth_stats_launch(mc_ctx* ctx, int64_t R, const int32_t* tid, const int64_t* start,
                               const int64_t* end, RegionOut* d_out, int64_t nf) {
     hipStream_t s = ctx->stream;
@@ -1589,7 +1535,7 @@ static int depth_stats_launch(mc_ctx* ctx, int64_t R, const int32_t* tid, const 
     if (nf == 0) fr.n = 0;
     auto& T = ctx->ts[ctx->ts_cur];
     if (int rc = launch_depth(ctx, fr, T.e[1], T.e[2])) return rc;
-    // the completion stamp (MC_DONE_MODE 0 / 1)
+    // the completion stamp
     const unsigned long long seq = ++ctx->done_seq;
     unsigned long long* stamp = nullptr;
     if (ctx->stamp_ok) {
@@ -1602,7 +1548,7 @@ static int depth_stats_launch(mc_ctx* ctx, int64_t R, const int32_t* tid, const 
                 __atomic_store_n(ctx->h_done.h, 0ull, __ATOMIC_RELEASE);
             }
         }
-        if (ctx->stamp_ok && MC_DONE_MODE == 1) stamp = ctx->h_done.d;
+        if (ctx->stamp_ok) stamp = ctx->h_done.d;
     }
     // K3b: its span is timed from K2's end event (one event fewer per call)
     // the device-side recompute of out-of-window regions: on for long reads
@@ -1639,11 +1585,9 @@ static int depth_stats_launch(mc_ctx* ctx, int64_t R, const int32_t* tid, const 
         ctx->fb_calls += 1;
     }
     // one wave per region; flags [0, R) and K2's max depth [R] land in mapped host memory
-    // the call's end event: on its last kernel (MC_EXT_EVENTS)
-    hipEvent_t k3_stop = MC_STEP_EVENTS && MC_EXT_EVENTS ? T.e[3] : nullptr;
 #define MC_LAUNCH_K3B(V)                                                                           \
     hipExtLaunchKernelGGL(region_final_wave_kernel<V>, dim3((unsigned)((R + kWaves - 1) / kWaves)),     \
-                          dim3(kBlock), 0u, s, nullptr, devfb ? nullptr : k3_stop, 0u,                   \
+                          dim3(kBlock), 0u, s, nullptr, nullptr, 0u,                                     \
                           ctx->d_fhist.p, R, ctx->d_acc.p,                                              \
                        reinterpret_cast<const int64_t*>(d + o_ntot),                                \
                        reinterpret_cast<const int64_t*>(d + o_nzx), d_out, ctx->h_fflag.d,           \
@@ -1661,11 +1605,11 @@ static int depth_stats_launch(mc_ctx* ctx, int64_t R, const int32_t* tid, const 
     if (devfb) {
         hipLaunchKernelGGL(fb_seg_kernel, dim3(1024), dim3(kBlock), (size_t)kLdsBins * 4, s, F);
         HIP_TRY(hipGetLastError());
-        hipExtLaunchKernelGGL(fb_final_kernel, dim3(kFbSlots), dim3(kBlock), 0u, s, nullptr, k3_stop, 0u, F);
+        hipExtLaunchKernelGGL(fb_final_kernel, dim3(kFbSlots), dim3(kBlock), 0u, s, nullptr, nullptr, 0u, F);
         HIP_TRY(hipGetLastError());
     }
-    if (MC_STEP_EVENTS && !MC_EXT_EVENTS) HIP_TRY(hipEventRecord(T.e[3], s));
-    if ((MC_DONE_MODE == 0 || (MC_DONE_MODE == 1 && devfb)) && ctx->stamp_ok && hipStreamWriteValue64(s, ctx->h_done.d, seq, 0) != hipSuccess) {
+    HIP_TRY(hipEventRecord(T.e[3], s));
+    if (devfb && ctx->stamp_ok && hipStreamWriteValue64(s, ctx->h_done.d, seq, 0) != hipSuccess) {
         (void)hipGetLastError();
         ctx->stamp_ok = false;
     }
@@ -1674,7 +1618,7 @@ static int depth_stats_launch(mc_ctx* ctx, int64_t R, const int32_t* tid, const 
     // the flags are in host memory once K3b's stamp is (no copy command);
     // the previous call's event times are read meanwhile
     resolve_timings(ctx, false);
-    if (int rc = MC_DONE_MODE == 2 ? wait_event_spin(T.e[3]) : wait_stamp(ctx, seq)) return rc;
+    if (int rc = wait_stamp(ctx, seq)) return rc;
     const int* flags = ctx->h_fflag.h;
     if (verdict && !check_direct(ctx, fflag_dres(ctx->h_fflag.h, R), true)) {
         direct_fallback(ctx, fflag_dres(ctx->h_fflag.h, R));

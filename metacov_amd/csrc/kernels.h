@@ -19,7 +19,9 @@
 
 namespace mc {
 
-// Tuning knobs (compile-time; scripts/ab_inproc.py A/Bs builds of them).
+// Compile-time geometry and widths (scripts/ab_inproc.py A/Bs builds of
+// them).  The alternative implementations that used to be switched here are
+// settled and gone; DESIGN.md §4.9 lists them with their measurements.
 #ifndef MC_TILE_W
 #define MC_TILE_W 4096                 // positions per tile (multiple of 1024)
 #endif
@@ -29,55 +31,8 @@ namespace mc {
 #ifndef MC_TILES_PER_CHUNK
 #define MC_TILES_PER_CHUNK 8
 #endif
-#ifndef MC_PREFETCH
-#define MC_PREFETCH 1                  // load read batch k+1 while applying batch k
-#endif
-#ifndef MC_PREFETCH_STATS
-#define MC_PREFETCH_STATS 1            // the same for the fused-statistics K2
-#endif
-#ifndef MC_APPLY_SHORT
-#define MC_APPLY_SHORT 1               // K2 without long reads: one branch per read in the apply loop
-                                       // (A/B, profiles/r05/r05ab1: direct C3 1.019 -> 1.002 ms, C2 0.0653 ->
-                                       // 0.0611; 2 = no branch, zero adds: 1.004 vs 0.990 ms, r05ab2)
-#endif
-#ifndef MC_FAR_HALO
-#define MC_FAR_HALO 1                  // direct K2: the chunk halo's far part by spans only (far_halo)
-#endif
 #ifndef MC_FAR_HALO_MIN
 #define MC_FAR_HALO_MIN 4096
-#endif
-#ifndef MC_DIRECT_ONE_CONTIG
-#define MC_DIRECT_ONE_CONTIG 1         // direct K2: a batch on the cached contig skips the contig lookup loop
-                                       // (C3 1.019 -> 1.007 ms, C2 0.0653 -> 0.0615; both: 0.988 / 0.0558)
-#endif
-#ifndef MC_K2_WAVE_ADVANCE
-#define MC_K2_WAVE_ADVANCE 0           // K2's read batches advance per wave (no block vote in the apply loop)
-#endif
-#ifndef MC_FILL_WAVE_COUNTS
-#define MC_FILL_WAVE_COUNTS 0          // long_fill_words_kernel: one count atomic per distinct tile of a wave
-#endif
-#ifndef MC_FILL_SORTED
-#define MC_FILL_SORTED 0               // long_fill_words_kernel: a round's events grouped by tile in LDS before the stores
-                                       // (measured at C5: 0.114 -> 0.128 ms, prepare 0.410 -> 0.421 ms; the 32 KB
-                                       // buffer halves the resident workgroups: profiles/r06/r06h_*)
-#endif
-#ifndef MC_DEFER_LONG
-#define MC_DEFER_LONG 1                // the fused long-read K2 defers its tile stores too (in-process A/B,
-                                       // C5 K2 median 1.087 -> 1.070 and 1.081 -> 1.072 ms: profiles/r06/r06j_*, r06k_*;
-                                       // the fused short-read K2 has no long-read registers to trade and loses 1.6 %)
-#endif
-#ifndef MC_DEFER_DIRECT
-#define MC_DEFER_DIRECT 0              // the fused direct K2 defers its tile stores too (in-process A/B: C3 K2
-                                       // 0.990 -> 1.009 ms, C2 0.0527 -> 0.0534: profiles/r06/r06l_*)
-#endif
-#ifndef MC_NT_STORE
-#define MC_NT_STORE 1                  // non-temporal depth stores (written once, not re-read soon)
-#endif
-#ifndef MC_WAVES_PLAIN
-#define MC_WAVES_PLAIN 0               // __launch_bounds__ waves/SIMD, plain K2 (0 = none)
-#endif
-#ifndef MC_WAVES_STATS
-#define MC_WAVES_STATS 4               // __launch_bounds__ waves/SIMD, fused K2 (<= 128 VGPRs)
 #endif
 // K2 reads each read of a prepared batch as ONE 4-byte word, written by
 // ingest_kernel: the low kGposBits bits of its global start (chunk-relative
@@ -257,15 +212,11 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
 #define MC_INGEST_U 1                  // C3 prepare: 1 0.406, 2 0.426, 4 0.82 ms (VGPR-bound occupancy)
 #endif
 constexpr int kIngestU = MC_INGEST_U;
-#ifndef MC_INGEST_NT_LOAD
 // ingest's read loads non-temporal (streamed once): C3 prepare -4.5 %.  The
 // same for K2's read batches (plain +3 %), the long-read kernels (+2 %) and
 // K1's CIGAR words (+13 %) measured worse.
-#define MC_INGEST_NT_LOAD 1
-#endif
 __device__ __forceinline__ i32x4 ingest_load(const int32_t* p) {
-    if (MC_INGEST_NT_LOAD) return __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(p));
-    return *reinterpret_cast<const i32x4*>(p);
+    return __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(p));
 }
 
 struct IngestAcc {                     // running record of contig cur (wave-uniform)
@@ -740,7 +691,7 @@ struct ProbeArgs {
     int64_t n_base;                    // grid targets k = 0 .. n_base
     int32_t* j0;                       // [n_base + 1] J(k * w)
     int32_t* jh;                       // [n_base + 1] J(k * w - halo)
-    int32_t* jn;                       // [n_base + 1] J(k * w - kNearHalo) (MC_FAR_HALO)
+    int32_t* jn;                       // [n_base + 1] J(k * w - kNearHalo) (far_halo)
     int32_t* fsamp;                    // [nc + 1] first sample of contig t
     unsigned long long* dres;
     unsigned long long gen;
@@ -859,7 +810,7 @@ probe_kernel(ProbeArgs A) {
     const bool first = j == 0;
     probe_fill(A.j0, A.n_base, A.lw, 0, key, key_next, first, last, (int32_t)(j + 1));
     probe_fill(A.jh, A.n_base, A.lw, A.halo, key, key_next, first, last, (int32_t)(j + 1));
-    if (MC_FAR_HALO) probe_fill(A.jn, A.n_base, A.lw, kNearHalo, key, key_next, first, last, (int32_t)(j + 1));
+    probe_fill(A.jn, A.n_base, A.lw, kNearHalo, key, key_next, first, last, (int32_t)(j + 1));
     // contigs (tid_j, tid_next] start after sample j
     const int ct = t < 0 ? 0 : t >= A.nc ? A.nc - 1 : t;
     const int cn = last ? A.nc : (t_next < 0 ? 0 : t_next >= A.nc ? A.nc - 1 : t_next);
@@ -1238,7 +1189,10 @@ long_fill_kernel(LongGeo G, const int64_t* __restrict__ tile_off, unsigned* __re
 // atomic pass; SQ: LDS bank-conflict cycles 2.5x the LDS-active cycles, waves
 // waiting on LDS 36 % of their cycles): C5 call 1.670 -> 1.634 ms.  Measured
 // and dropped: one or eight sub-ranges per round (no change), counters striped
-// over 8 / 16 lanes (1.680 / 1.686 ms; profiles/r04/r04o_long_fill_ab.txt).
+// over 8 / 16 lanes (1.680 / 1.686 ms; profiles/r04/r04o_long_fill_ab.txt),
+// a round's events grouped by tile in LDS before the stores (0.114 -> 0.128
+// ms, prepare 0.410 -> 0.421 ms; its 32 KB buffer halves the resident
+// workgroups: profiles/r06/r06h_*).
 constexpr int kFillSubs = 4;
 
 __global__ void __launch_bounds__(kBlock)
@@ -1250,11 +1204,6 @@ long_fill_words_kernel(const uint32_t* __restrict__ ew, int64_t n, int64_t per, 
     __shared__ int wt[kLongTileWin];      // per window tile: count (ranks come back from the atomics)
     __shared__ int wb[kLongTileWin];      // per window tile: first slot
     __shared__ unsigned red[kWaves];
-    // MC_FILL_SORTED: per window tile its first position in the round's LDS
-    // event buffer; the buffer (values and their global slots)
-    __shared__ int wc[MC_FILL_SORTED ? kLongTileWin : 1];
-    __shared__ int32_t sbuf[MC_FILL_SORTED ? kBlock * 4 * kFillSubs : 1];
-    __shared__ int32_t sslot[MC_FILL_SORTED ? kBlock * 4 * kFillSubs : 1];
     const int64_t cmask = ((int64_t)1 << lcw) - 1;
     for (int k = threadIdx.x; k < kLongTileWin; k += kBlock) wt[k] = 0;
     const int64_t r0 = blockIdx.x * per, r1 = min(n, r0 + per);
@@ -1284,8 +1233,6 @@ long_fill_words_kernel(const uint32_t* __restrict__ ew, int64_t n, int64_t per, 
         const int64_t TB = m == ~0u ? 0 : (int64_t)(m / kTileW);
         int te[kE];     // window tile, or -1
         int rk[kE];     // rank in its tile
-        const int lane = threadIdx.x & 63;
-        const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
         for (int k = 0; k < kE; ++k) {
             te[k] = -1;
@@ -1294,23 +1241,7 @@ long_fill_words_kernel(const uint32_t* __restrict__ ew, int64_t n, int64_t per, 
                 const int64_t t = (int64_t)(e[k] / kTileW);
                 if (t - TB < kLongTileWin) te[k] = (int)(t - TB);
             }
-            if (MC_FILL_WAVE_COUNTS) {
-                // one LDS atomic per distinct tile of the wave (the lanes of
-                // a tile take consecutive ranks after the leader's add)
-                unsigned long long todo = __ballot(te[k] >= 0);
-                while (todo) {
-                    const int leader = __ffsll((long long)todo) - 1;
-                    const int tt = __builtin_amdgcn_readlane(te[k], leader);
-                    const unsigned long long m = __ballot(te[k] == tt);
-                    int base = 0;
-                    if (lane == leader) base = atomicAdd(&wt[tt], (int)__popcll(m));
-                    base = __builtin_amdgcn_readlane(base, leader);
-                    if (te[k] == tt) rk[k] = base + (int)__popcll(m & below);
-                    todo &= ~m;
-                }
-            } else if (te[k] >= 0) {
-                rk[k] = atomicAdd(&wt[te[k]], 1);
-            }
+            if (te[k] >= 0) rk[k] = atomicAdd(&wt[te[k]], 1);
         }
         __syncthreads();
         for (int t = threadIdx.x; t < kLongTileWin; t += kBlock) {
@@ -1319,48 +1250,6 @@ long_fill_words_kernel(const uint32_t* __restrict__ ew, int64_t n, int64_t per, 
                 wb[t] = (int)(tile_off[TB + t] + atomicAdd(&cursor[TB + t], (unsigned)v));
                 wt[t] = 0;
             }
-            if (MC_FILL_SORTED) wc[t] = v;
-        }
-        if (MC_FILL_SORTED) {
-            // the round's window events grouped by tile in LDS, then written
-            // out in that order: consecutive lanes store consecutive slots of a
-            // tile's run (one scattered 4-byte store per event left each wave
-            // store instruction spread over ~a dozen tiles' runs)
-            __syncthreads();
-            // exclusive prefix of the window's counts: one tile per thread,
-            // wave scans by shuffles, then the waves' totals
-            static_assert(kBlock == kLongTileWin, "one window tile per thread");
-            const int own = wc[threadIdx.x];
-            int inc = own;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int y = __shfl_up(inc, d, 64);
-                if (lane >= d) inc += y;
-            }
-            if (lane == 63) red[threadIdx.x >> 6] = (unsigned)inc;
-            __syncthreads();
-            int add = 0;
-            for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) add += (int)red[w];
-            wc[threadIdx.x] = add + inc - own;
-            const int total = (int)(red[0] + red[1] + red[2] + red[3]);
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < kE; ++k) {
-                if (e[k] == ~0u) continue;
-                const int32_t val = (int32_t)((int64_t)e[k] & cmask);   // chunk-relative end
-                if (te[k] >= 0) {
-                    const int at = wc[te[k]] + rk[k];
-                    sbuf[at] = val;
-                    sslot[at] = wb[te[k]] + rk[k];
-                } else {
-                    const int64_t t = (int64_t)(e[k] / kTileW);
-                    ev[tile_off[t] + atomicAdd(&cursor[t], 1u)] = val;
-                }
-            }
-            __syncthreads();
-            for (int j = threadIdx.x; j < total; j += kBlock) ev[sslot[j]] = sbuf[j];
-            __syncthreads();   // sbuf / wb / wc are rewritten by the next round
-            continue;
         }
         __syncthreads();
 #pragma unroll
@@ -1636,10 +1525,11 @@ __device__ __forceinline__ void finish_batch_direct(ReadBatch& b, const RawBatch
     const unsigned inr = range4(dc.lo, dc.hi);
     const unsigned own = range4(dc.vlo, dc.vhi);
     bool fast = false;   // wave-uniform
-    if (MC_DIRECT_ONE_CONTIG && acc.ct >= 0) {
+    if (acc.ct >= 0) {
         // every read this batch applies or checks is on the contig of the
         // previous batch (sorted reads: almost every batch): one vote instead
-        // of the lookup loop's two and its per-read selects
+        // of the lookup loop's two and its per-read selects (C3 1.019 ->
+        // 1.007 ms, C2 0.0653 -> 0.0615)
         const unsigned use = (inr | own) & valid;
         bool other = false;
 #pragma unroll
@@ -2153,9 +2043,8 @@ struct K2Consts {
 };
 
 template <bool kStats, bool kLong, bool kDirect>
-// waves/SIMD minimum per variant (0 = unconstrained -> 1)
-__global__ void __launch_bounds__(kK2Block, kStats ? (MC_WAVES_STATS ? MC_WAVES_STATS : 1)
-                                                 : (MC_WAVES_PLAIN ? MC_WAVES_PLAIN : 1))
+// waves/SIMD minimum: the fused K2 at 4 (<= 128 VGPRs), the plain K2 unconstrained
+__global__ void __launch_bounds__(kK2Block, kStats ? 4 : 1)
 depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
              const int64_t* __restrict__ coff, const int64_t* __restrict__ chunk_first,
              int cstride, int64_t n_chunks, int tiles_per_chunk, int short_max,
@@ -2187,9 +2076,11 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
     // Deferred tile stores (a tile's stores issued after the next tile's
     // apply loop), plain K2 only: with 12 B/read they gained plain C3 -2.4 %,
     // C5 -4.9 %; with the packed read words the fused C3 K2 runs 1.6 % faster
-    // without them (profiles/r02zz_knobs_ab.txt).
-    constexpr bool kDefer = !kStats || (kLong && MC_DEFER_LONG) || (kDirect && MC_DEFER_DIRECT);
-    constexpr bool kPf = kStats ? MC_PREFETCH_STATS : MC_PREFETCH;
+    // without them (profiles/r02zz_knobs_ab.txt).  The fused long-read K2
+    // defers them too (in-process A/B, C5 K2 median 1.087 -> 1.070 and 1.081
+    // -> 1.072 ms: profiles/r06/r06j_*, r06k_*); the fused direct K2 does not
+    // (C3 K2 0.990 -> 1.009 ms, C2 0.0527 -> 0.0534: profiles/r06/r06l_*).
+    constexpr bool kDefer = !kStats || kLong;
     // The probe saw an unsorted / invalid sample or a long span: the host
     // re-runs this batch through the full prepare; nothing to do here.
     if (kDirect) {
@@ -2245,7 +2136,7 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
             dc.vhi = last ? n : lower(uload(D.j0, b1));
             dc.lo = min(dc.lo, dc.vlo);   // (apart only on unsorted input, which is reported)
             dc.hi = max(dc.hi, dc.vhi);
-            if (MC_FAR_HALO && c) {   // [lo, lower(J(C0 - kNearHalo))): by spans (far_halo)
+            if (c) {   // [lo, lower(J(C0 - kNearHalo))): by spans (far_halo)
                 const int64_t fh = min(max(lower(uload(D.jn, b0)), dc.lo), dc.vlo);
                 // (a far part under kFarHaloMin reads costs more than it saves:
                 // C3 +1.4 % at 1024, neutral at 4096; C2 K2 -3 %, r05/r05ab12_*)
@@ -2290,10 +2181,10 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
         RawBatch<kDirect> r0;
         if (more) {
             issue_raw<kDirect>(r0, base, A, cend);
-            if (kPf && base + kK2Batch < cend) issue_raw<kDirect>(nxt, base + kK2Batch, A, cend);
+            if (base + kK2Batch < cend) issue_raw<kDirect>(nxt, base + kK2Batch, A, cend);
         }
         // (after the first batches' loads are issued: one round trip for both)
-        if (kDirect && MC_FAR_HALO && far_hi > far_lo) far_halo(A, D, coff, far_lo, far_hi, C0, short_max, ring);
+        if (kDirect && far_hi > far_lo) far_halo(A, D, coff, far_lo, far_hi, C0, short_max, ring);
         if (more) finish(r0, base);
         int carry = kLong ? uload(chunk_carry, c) : 0;
         // -1 end events of long reads (chunk-relative, in tile order): a
@@ -2316,12 +2207,8 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
         auto store_tile = [&](int64_t tile0) {
             int32_t* dst = depth + tile0 + wave * kWaveSpan + lane * 4;
 #pragma unroll
-            for (int j = 0; j < kChunks; ++j) {
-                if (MC_NT_STORE)
-                    __builtin_nontemporal_store(v[j], reinterpret_cast<i32x4*>(dst + j * 256));
-                else
-                    *reinterpret_cast<i32x4*>(dst + j * 256) = v[j];
-            }
+            for (int j = 0; j < kChunks; ++j)   // non-temporal: written once, not re-read soon
+                __builtin_nontemporal_store(v[j], reinterpret_cast<i32x4*>(dst + j * 256));
         };
         for (int t = 0; t < tiles_per_chunk; ++t) {
             const int64_t T0 = C0 + (int64_t)t * kTileW;
@@ -2336,24 +2223,19 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
                             eb.pending &= ~(1u << k);
                         }
                 }
-                if (MC_APPLY_SHORT && !kLong) {
+                if (!kLong) {
                     // every pending read is short here (the direct path's masks;
                     // a packed batch without long reads): one branch per read
+                    // (A/B, profiles/r05/r05ab1: direct C3 1.019 -> 1.002 ms, C2
+                    // 0.0653 -> 0.0611; no branch and zero adds: 1.004 vs 0.990
+                    // ms, r05ab2)
                     unsigned done = 0;
 #pragma unroll
                     for (int k = 0; k < kReadsPerThread; ++k) {
                         const bool go = ((b.pending >> k) & 1u) && b.rs[k] < tend_rel;
                         done |= go ? 1u << k : 0u;
                         const int s = b.rs[k] > 0 ? b.rs[k] : 0, e = b.rs[k] + b.sp[k];
-                        if (MC_APPLY_SHORT == 2) {
-                            // no branch: a read that applies nothing adds 0 to
-                            // its slots (a wave-uniform skip when no lane applies)
-                            const bool ap = go && e > s;
-                            if (__ballot(ap)) {
-                                atomicAdd(&ring[ring_slot(s)], ap ? 1 : 0);
-                                atomicAdd(&ring[ring_slot(e)], ap ? -1 : 0);
-                            }
-                        } else if (go && e > s) {
+                        if (go && e > s) {
                             atomicAdd(&ring[ring_slot(s)], 1);
                             atomicAdd(&ring[ring_slot(e)], -1);
                         }
@@ -2378,16 +2260,8 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
                     }
                 }
                 bool all_done, ev_done;
-                if (MC_K2_WAVE_ADVANCE) {
-                    // each wave streams its own quarter of every batch (reads
-                    // base + 256 w ..): it advances as soon as its lanes are
-                    // done, no barrier; the tile scan's barrier orders the ring
-                    all_done = __all(b.pending == 0);
-                    ev_done = __all(eb.pending == 0);
-                } else {
-                    block_all2(hdr + 4 + 2 * kK2Waves, and_flip, b.pending == 0, eb.pending == 0, wave, lane,
-                               all_done, ev_done);
-                }
+                block_all2(hdr + 4 + 2 * kK2Waves, and_flip, b.pending == 0, eb.pending == 0, wave, lane,
+                           all_done, ev_done);
                 const bool adv_reads = all_done && more;
                 const bool adv_events = ev_done && ev_more;
                 if (!adv_reads && !adv_events) break;
@@ -2400,15 +2274,11 @@ depth_kernel(ReadArrays A, const K2Consts* __restrict__ K, int64_t n,
                     base += kK2Batch;
                     more = base < cend;
                     if (more) {
-                        if (!kPf) issue_raw<kDirect>(nxt, base, A, cend);
                         finish(nxt, base);   // loaded one batch ago
-                        if (kPf && base + kK2Batch < cend) issue_raw<kDirect>(nxt, base + kK2Batch, A, cend);
+                        if (base + kK2Batch < cend) issue_raw<kDirect>(nxt, base + kK2Batch, A, cend);
                     }
                 }
             }
-            // (per-wave advance: every wave's ring adds for this tile are in
-            // before any wave reads its span of the tile)
-            if (MC_K2_WAVE_ADVANCE) __syncthreads();
             // the previous tile's depth, held in v since its scan: its stores go
             // out only now, so a vmcnt wait in the apply loop above (batch
             // advance) found them a whole tile phase old instead of just issued

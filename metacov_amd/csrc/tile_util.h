@@ -1,8 +1,8 @@
 // What the tile modules (runs.hip, windows.hip, bases.hip) share: the HIP
-// error macro (also ecor.hip's, exp_gpu.hip's and bam_gpu.hip's), the
-// grow-only device array and the one-workgroup prefix scan over per-tile
-// counts.  engine.hip and scan.hip keep copies of the macro of their own:
-// their sources are fingerprinted with the recorded measurements.
+// error macro (also engine.hip's, ecor.hip's, exp_gpu.hip's and
+// bam_gpu.hip's), the grow-only device array and the one-workgroup prefix
+// scan over per-tile counts.  Only scan.hip keeps a copy of the macro of its
+// own.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--nocheck", action="store_true", help="deliberately-wrong experiment builds")
     ap.add_argument("--loop", action="store_true", help="direct mode: also time back-to-back calls into a device table")
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c5"])
+    ap.add_argument("--json", default=None, help="also write each build's per-round figures to this file")
     a = ap.parse_args()
     import torch
     from bench import CONFIGS, config_contigs, device_workload
@@ -49,6 +50,7 @@ def main():
         e.set_contigs(lengths)
         e.add_reads(tid, pos, span)
         engines.append(e)
+    record = {"config": a.config, "reads": int(reads), "rounds": a.rounds, "steps": a.steps, "modes": {}}
     modes = {"both": ["plain", "fused"], "all": ["plain", "fused", "direct"]}.get(a.mode, [a.mode])
     for mode in modes:
         times = {lib: [] for lib in a.libs}
@@ -96,12 +98,21 @@ def main():
                 l = np.array(loops[lib])
                 print("loop   %-48s per call median %.4f ms  min %.4f ms  (rounds %d x %d calls)"
                       % (os.path.basename(lib), np.median(l), l.min(), len(l), a.steps), flush=True)
+                record["modes"].setdefault("loop", {})[os.path.basename(lib)] = {
+                    "call_ms_median": float(np.median(l)), "call_ms_per_round": [float(x) for x in l]}
         for lib in a.libs:
             t = np.array(times[lib])
             w = np.array(walls[lib])
             fb = engines[a.libs.index(lib)].fused_fallbacks() if mode != "plain" else 0
             print("%-6s %-48s K2 median %.4f ms  min %.4f ms  call median %.4f ms  fallbacks %d  (n=%d)"
                   % (mode, os.path.basename(lib), np.median(t), t.min(), np.median(w), fb, len(t)), flush=True)
+            record["modes"].setdefault(mode, {})[os.path.basename(lib)] = {
+                "k2_ms_median": float(np.median(t)), "call_ms_median": float(np.median(w)),
+                "k2_ms_per_round": [float(x) for x in np.median(t.reshape(a.rounds, a.steps), axis=1)]}
+    if a.json:
+        import json
+        with open(a.json, "w") as f:
+            json.dump(record, f, indent=1)
 
 
 if __name__ == "__main__":

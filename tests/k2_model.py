@@ -11,7 +11,7 @@ bugs show up without a GPU.  Constants must match kernels.h.
 import numpy as np
 from oracle import coracle
 W=4096; TPC_MAX=8; RING=8192; SM=RING-W
-GB=18; GMASK=(1<<GB)-1; SCAP=(1<<(32-GB))-1   # K2's read words (kernels.h MC_GPOS 2)
+GB=18; GMASK=(1<<GB)-1; SCAP=(1<<(32-GB))-1   # K2's read words (kernels.h kGposBits, kGposMask, kGspanCap)
 
 
 def read_words(gs, span):
