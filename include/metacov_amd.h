@@ -495,7 +495,66 @@ int mc_windows_dims(int32_t* tile, int32_t* min_window, int32_t* max_bins, int32
  * long as mc_bases_src_batch's arrays); the GPU decoder's bases mode always
  * fills a flag column (mc_bam_gpu_bases_flags, _bases_copy_flags).
  *   Not covered: the strand of insertion alleles, strand in the consensus
- * rule, strand-bias statistics (floating point: host work over these counts). */
+ * rule, strand-bias statistics (floating point: host work over these counts).
+ *
+ * Quality sums (opt-in, as strand is): how good the evidence behind a count
+ * is, the sums behind bam-readcount's avg_basequality / avg_mapping_quality and
+ * pysamstats' baseq / mapq.  mc_bases_track_quality(h, on): on = 1 / 0 makes
+ * the NEXT mc_bases_begin also allocate and zero two plane sets (or not);
+ * another value is MC_E_INVALID.  Both are uint32 and indexed exactly like the
+ * count planes:
+ *   bq[6][N]  the sum of the quality bytes of the bases counted into channel c
+ *             at a position.  Only counted bases contribute (those that pass
+ *             min_baseq); a read whose qualities are absent (first QUAL byte
+ *             0xFF) is counted as without tracking and adds 0; plane
+ *             MC_BASES_DEL stays 0 (a deletion has no base).
+ *   mq[6][N]  the sum of the MAPQ bytes of the reads counted into channel c,
+ *             DEL included.  The byte is summed as it is: 255 is not special.
+ * The sums are exact while a channel's count x 255 < 2^32 and wrap modulo 2^32
+ * beyond; they are independent of the batch split and repeatable.  The count
+ * planes are unchanged by tracking: mc_bases_get, _sites, _consensus and
+ * _insertions give the same results with it on as off.  Quality and strand
+ * tracking in one pass are out of scope: a begin with both on is MC_E_STATE
+ * (the message names both).
+ *   Reads: mc_bases_add_batch_mapq / _add_batch_device_mapq take the nine
+ * arrays plus mapq[n] (uint8; a device pointer for the device call; a
+ * sub-range of a resident table is d_mapq + a); checks and error messages are
+ * mc_bases_add_batch's.  On a handle that tracks quality the calls without
+ * mapq are MC_E_STATE; on one that does not, the new calls ignore the column.
+ *   Fetch: mc_bases_get_quality copies positions [first, first + count) of
+ * both sets to bq[6][count] and mq[6][count]; mc_bases_quality_device exposes
+ * them (plane c at d_bq + c * stride, d_mq + c * stride).
+ * mc_bases_set_quality (test hook): sets the counts and both sum sets from
+ * total, bq, mq [6][count]; bq[c] > 255 * total[c], mq[c] > 255 * total[c] or
+ * bq[DEL] != 0 anywhere is MC_E_INVALID (checked on the host, nothing is
+ * written); results are gone as after mc_bases_set (which leaves the sums
+ * alone).  All three are MC_E_STATE without tracking.
+ *   Sites: mc_bases_sites_quality.  Depth and the base allele are exactly
+ * mc_bases_sites'.  Position p is a site iff depth >= min_depth and some
+ * allele i != base has a[i] >= min_count, a[i] * 10^6 >= min_ppm * depth,
+ * mq[i] >= min_alt_mapq * a[i] and, for i != DEL, bq[i] >= min_alt_baseq *
+ * a[i]; all in 64-bit integers (the mean reaches the threshold, without a
+ * division).  Thresholds outside 0..255 are MC_E_INVALID, a handle without
+ * tracking MC_E_STATE.  With both thresholds 0 the site list is
+ * mc_bases_sites' exactly.  The result lands in mc_bases_sites' buffers;
+ * mc_bases_sites_get_quality copies the sites' sums bq[count][6] and
+ * mq[count][6] (MC_E_STATE after a plain or a strand sites call).
+ *   Device side: a third instantiation of the pileup kernel, no global
+ * atomics, one owner per plane element.  One 64-bit LDS add per counted base
+ * carries the count (bits 0..15), the quality byte (16..39) and the MAPQ
+ * (40..63).  With 8-byte cells a workgroup holds 1024 positions in the same
+ * 48 KiB, so a 2048-position tile is two workgroups, each with its half of
+ * the tile's aligned window.  A read covers a position at most once, so over
+ * at most 65535 reads no field carries (65535 x 255 < 2^24): a workgroup walks
+ * its reads in groups of that size and flushes the three fields into the
+ * three plane sets after each (mc_bases_quality_dims: 1024, 65535).
+ *   Sources: mc_bases_src_mapq gives the MAPQ column of the last batch (valid
+ * as long as mc_bases_src_batch's arrays); the GPU decoder's bases mode always
+ * fills a mapq column beside its flag column (mc_bam_gpu_bases_mapq,
+ * _bases_copy_mapq).
+ *   Not covered: quality with strand in one pass, quality in the consensus
+ * rule or the insertion table, means or medians (the reader's division),
+ * bam-readcount's read-position and mismatch columns. */
 #define MC_BASES_A   0
 #define MC_BASES_C   1
 #define MC_BASES_G   2
@@ -556,6 +615,28 @@ int mc_bases_sites_strand(mc_bases* h, int64_t min_depth, int64_t min_count, int
                           int64_t min_alt_strand, const uint8_t* ref /* N, or NULL */, int64_t* n_sites);
 int mc_bases_sites_get_reverse(const mc_bases* h, int64_t first, int64_t count,
                                uint32_t* rev_counts /* count x 6 */);
+int mc_bases_track_quality(mc_bases* h, int on);
+int mc_bases_add_batch_mapq(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                            const int64_t* cig_off /* n + 1 */, const uint32_t* cigar, const int32_t* l_seq,
+                            const int64_t* seq_off /* n + 1 */, const uint8_t* seq,
+                            const int64_t* qual_off /* n + 1 */, const uint8_t* qual, const uint8_t* mapq /* n */);
+int mc_bases_add_batch_device_mapq(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                                   const int64_t* d_cig_off /* n + 1 */, const uint32_t* d_cigar, int64_t n_words,
+                                   const int32_t* d_l_seq, const int64_t* d_seq_off /* n + 1 */,
+                                   const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off /* n + 1 */,
+                                   const uint8_t* d_qual, int64_t qual_bytes, const uint8_t* d_mapq /* n */);
+int mc_bases_get_quality(const mc_bases* h, int64_t first, int64_t count, uint32_t* bq /* 6 x count */,
+                         uint32_t* mq /* 6 x count */);
+int mc_bases_quality_device(const mc_bases* h, const uint32_t** d_bq, const uint32_t** d_mq, int64_t* stride,
+                            int64_t* n);
+int mc_bases_set_quality(mc_bases* h, int64_t first, int64_t count, const uint32_t* total /* 6 x count */,
+                         const uint32_t* bq /* 6 x count */, const uint32_t* mq /* 6 x count */);
+int mc_bases_sites_quality(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                           int64_t min_alt_baseq, int64_t min_alt_mapq, const uint8_t* ref /* N, or NULL */,
+                           int64_t* n_sites);
+int mc_bases_sites_get_quality(const mc_bases* h, int64_t first, int64_t count, uint32_t* bq /* count x 6 */,
+                               uint32_t* mq /* count x 6 */);
+int mc_bases_quality_dims(int32_t* tile /* positions per workgroup */, int32_t* group /* reads per flush */);
 
 /* Consensus (mc_bases_consensus), a third stage over the planes on the device:
  * one letter per position, called from the counts alone.  Without
@@ -719,6 +800,7 @@ int mc_bases_src_batch(const mc_bases_src* s, const int32_t** tid, const int32_t
                        const uint32_t** cigar, const int32_t** l_seq, const int64_t** seq_off,
                        const uint8_t** seq, const int64_t** qual_off, const uint8_t** qual);
 int mc_bases_src_flags(const mc_bases_src* s, const uint16_t** flag /* n of the last batch */);
+int mc_bases_src_mapq(const mc_bases_src* s, const uint8_t** mapq /* n of the last batch */);
 int mc_bases_src_counts(const mc_bases_src* s, int64_t* records, int64_t* kept, int64_t* no_seq,
                         int64_t* bad_cigar);
 
@@ -949,6 +1031,9 @@ int mc_bam_gpu_bases_copy(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int64
  * [a, a + n) is *d_flag + a), or a copy to flag[n] on the host. */
 int mc_bam_gpu_bases_flags(const mc_bam_gpu* g, const uint16_t** d_flag);
 int mc_bam_gpu_bases_copy_flags(const mc_bam_gpu* g, uint16_t* flag /* n */);
+/* The mapq column beside it (1 byte per read, record byte 9 as it is). */
+int mc_bam_gpu_bases_mapq(const mc_bam_gpu* g, const uint8_t** d_mapq);
+int mc_bam_gpu_bases_copy_mapq(const mc_bam_gpu* g, uint8_t* mapq /* n */);
 int mc_bam_gpu_bases_counts(const mc_bam_gpu* g, int64_t* records, int64_t* kept, int64_t* no_seq,
                             int64_t* bad_cigar);
 /* The same for one rank's contigs (mc_bam_gpu_open_extents' blocks and

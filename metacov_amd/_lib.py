@@ -170,6 +170,17 @@ SIGNATURES = {
     "mc_bases_sites_strand": [_P, _I64, _I64, _I64, _I64, _P, _PI64],
     "mc_bases_sites_get_reverse": [_P, _I64, _I64, _P],
     "mc_bases_src_flags": [_P, _PP],
+    # quality sums (opt-in): the counted bases' quality bytes and their reads' MAPQ, per channel
+    "mc_bases_track_quality": [_P, ctypes.c_int],
+    "mc_bases_add_batch_mapq": [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mc_bases_add_batch_device_mapq": [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _I64, _P],
+    "mc_bases_get_quality": [_P, _I64, _I64, _P, _P],
+    "mc_bases_quality_device": [_P, _PP, _PP, _PI64, _PI64],
+    "mc_bases_set_quality": [_P, _I64, _I64, _P, _P, _P],
+    "mc_bases_sites_quality": [_P, _I64, _I64, _I64, _I64, _I64, _P, _PI64],
+    "mc_bases_sites_get_quality": [_P, _I64, _I64, _P, _P],
+    "mc_bases_quality_dims": [_PI32, _PI32],
+    "mc_bases_src_mapq": [_P, _PP],
     # insertion alleles (csrc/bases_ins.h)
     "mc_bases_track_insertions": [_P, ctypes.c_int],
     "mc_bases_insertions": [_P, _I64, _I64, _I64, _PI64],
@@ -228,6 +239,8 @@ SIGNATURES = {
     "mc_bam_gpu_bases_counts": [_P, _PI64, _PI64, _PI64, _PI64],
     "mc_bam_gpu_bases_flags": [_P, _PP],
     "mc_bam_gpu_bases_copy_flags": [_P, _P],
+    "mc_bam_gpu_bases_mapq": [_P, _PP],
+    "mc_bam_gpu_bases_copy_mapq": [_P, _P],
     "mc_bam_index_extents": [ctypes.c_char_p, _I32, _P, _PI64],
     "mc_bam_gpu_open_contigs": [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, _U32, _I32, _P,
                                 _PP],

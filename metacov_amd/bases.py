@@ -26,7 +26,11 @@ insertions=True) writes the called ones into the compact letters.  Strand is
 opt-in too: begin(..., strand=True) keeps the counts of the reverse-strand
 reads (flag & 0x10) beside the totals (counts_reverse(); forward = counts() -
 counts_reverse()), and sites(..., min_alt_strand=K) asks for an alternative
-allele seen K times on each strand.
+allele seen K times on each strand.  So are the quality sums: begin(...,
+quality=True) keeps, per channel, the sum of the counted bases' quality bytes
+and of their reads' MAPQ (quality() -> (bq, mq)); the reads then come with
+their mapq column, and sites(..., min_alt_baseq=Q, min_alt_mapq=Q) asks for an
+alternative allele whose mean qualities reach the thresholds.
 """
 import ctypes
 
@@ -49,6 +53,15 @@ def dims(lib=None):
     return t.value
 
 
+def quality_dims(lib=None):
+    """(positions per workgroup of the quality pileup kernel, reads it walks
+    between two flushes of its packed LDS cells)."""
+    lib = lib or _lib.load()
+    a, b = ctypes.c_int32(), ctypes.c_int32()
+    check(lib.mc_bases_quality_dims(ctypes.byref(a), ctypes.byref(b)), lib)
+    return a.value, b.value
+
+
 def ins_dims(lib=None):
     """(events one workgroup sorts in LDS, longest callable insertion)."""
     lib = lib or _lib.load()
@@ -62,13 +75,17 @@ class Sites:
     first[s] .. first[s + 1]; pos [n] int64 relative to the contig, ascending
     within a segment; counts [n, 6] uint32 (A, C, G, T, N, DEL); rev_counts
     [n, 6] uint32, the reverse-strand reads' share of counts, on a counter
-    that tracks strand, else None."""
+    that tracks strand, else None; bq_sums and mq_sums [n, 6] uint32, the
+    sites' quality and MAPQ sums, on a counter that tracks quality, else
+    None."""
 
-    def __init__(self, first, pos, counts, rev_counts=None):
+    def __init__(self, first, pos, counts, rev_counts=None, bq_sums=None, mq_sums=None):
         self.first = np.asarray(first, np.int64)
         self.pos = np.asarray(pos, np.int64)
         self.counts = np.asarray(counts, np.uint32).reshape(-1, 6)
         self.rev_counts = None if rev_counts is None else np.asarray(rev_counts, np.uint32).reshape(-1, 6)
+        self.bq_sums = None if bq_sums is None else np.asarray(bq_sums, np.uint32).reshape(-1, 6)
+        self.mq_sums = None if mq_sums is None else np.asarray(mq_sums, np.uint32).reshape(-1, 6)
 
     def __len__(self):
         return len(self.pos)
@@ -194,6 +211,17 @@ class BaseSource:
         buf = (ctypes.c_char * (2 * n)).from_address(p.value)
         return np.frombuffer(buf, dtype=np.uint16, count=n)
 
+    def mapq(self):
+        """uint8 [n]: the MAPQ bytes of the last batch next() returned (a view,
+        valid until the next call)."""
+        n = getattr(self, "_n", 0)
+        if n == 0:
+            return np.zeros(0, np.uint8)
+        p = ctypes.c_void_p()
+        check(self._lib.mc_bases_src_mapq(self._h, ctypes.byref(p)), self._lib)
+        buf = (ctypes.c_char * n).from_address(p.value)
+        return np.frombuffer(buf, dtype=np.uint8, count=n)
+
     def counts(self):
         """Records read so far: total, kept (past the filters), and the kept
         ones skipped for no SEQ or for a CIGAR whose query length differs from
@@ -251,6 +279,10 @@ class GpuBaseSource:
         if hasattr(self._lib, "mc_bam_gpu_bases_flags"):             # (an A/B build of an older revision has none)
             check(self._lib.mc_bam_gpu_bases_flags(self._h, r(f)), self._lib)
         self._dflag = f.value or 0               # the flag column, uint16 per read
+        f = ctypes.c_void_p()
+        if hasattr(self._lib, "mc_bam_gpu_bases_mapq"):              # (the same)
+            check(self._lib.mc_bam_gpu_bases_mapq(self._h, r(f)), self._lib)
+        self._dmapq = f.value or 0               # the mapq column, uint8 per read
         self._lib.mc_bam_gpu_trim(self._h, None)  # the decode's staging is not needed again
 
     def __len__(self):
@@ -286,6 +318,12 @@ class GpuBaseSource:
         check(self._lib.mc_bam_gpu_bases_copy_flags(self._h, ptr(out)), self._lib)
         return out
 
+    def copy_mapq(self):
+        """uint8 [n]: the reads' MAPQ bytes on the host."""
+        out = np.zeros(self.n, np.uint8)
+        check(self._lib.mc_bam_gpu_bases_copy_mapq(self._h, ptr(out)), self._lib)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.mc_bam_gpu_close(self._h)
@@ -314,6 +352,7 @@ class BaseCounter:
         self.device = int(device)
         self._S = 0
         self.strand = False
+        self._quality = False
         check(self._lib.mc_bases_create(self.device, self.n_ref, ctypes.byref(self._h)), self._lib)
 
     def close(self):
@@ -333,12 +372,15 @@ class BaseCounter:
     def __exit__(self, *exc):
         self.close()
 
-    def begin(self, tids, starts, ends, min_baseq=0, insertions=False, strand=False):
+    def begin(self, tids, starts, ends, min_baseq=0, insertions=False, strand=False, quality=False):
         """Allocates and zeroes the planes of the segments [start, end) of
         contig tid; returns N, the positions in all.  insertions: also collect
         the reads' insertion alleles (insertions(), consensus(insertions=True)).
         strand: also keep the reverse-strand reads' counts (counts_reverse(),
-        sites(min_alt_strand=...)); the reads then come with their flags."""
+        sites(min_alt_strand=...)); the reads then come with their flags.
+        quality: also keep the sums of the counted bases' quality bytes and of
+        their reads' MAPQ (quality(), sites(min_alt_baseq=..., min_alt_mapq=...));
+        the reads then come with their mapq column.  Not together with strand."""
         tids = np.ascontiguousarray(tids, dtype=np.int32)
         starts = np.ascontiguousarray(starts, dtype=np.int64)
         ends = np.ascontiguousarray(ends, dtype=np.int64)
@@ -347,19 +389,25 @@ class BaseCounter:
         check(self._lib.mc_bases_track_insertions(self._h, int(bool(insertions))), self._lib)
         if strand or hasattr(self._lib, "mc_bases_track_strand"):    # (an A/B build of an older revision has none)
             check(self._lib.mc_bases_track_strand(self._h, int(bool(strand))), self._lib)
-        self.strand = False
+        if quality or hasattr(self._lib, "mc_bases_track_quality"):  # (the same)
+            check(self._lib.mc_bases_track_quality(self._h, int(bool(quality))), self._lib)
+        self.strand = self._quality = False
         check(self._lib.mc_bases_begin(self._h, len(tids), ptr(tids), ptr(starts), ptr(ends), int(min_baseq)),
               self._lib)
         self.strand = bool(strand)
+        self._quality = bool(quality)
         self._S = len(tids)
         return int(self.seg_off[-1])
 
-    def add_reads(self, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, flag=None):
+    def add_reads(self, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, flag=None, mapq=None):
         """One batch of reads sorted by (tid, pos) (mc_bases_add_batch); flag:
         the reads' BAM flag words, required on a counter that tracks strand
-        (mc_bases_add_batch_flags)."""
+        (mc_bases_add_batch_flags); mapq: their MAPQ bytes, required on one
+        that tracks quality (mc_bases_add_batch_mapq)."""
         if self.strand and flag is None:
             raise ValueError("the counter tracks strand: add_reads needs the reads' flags")
+        if self._quality and mapq is None:
+            raise ValueError("the counter tracks quality: add_reads needs the reads' mapq")
         tid = np.ascontiguousarray(tid, dtype=np.int32)
         n = len(tid)
         pos = np.ascontiguousarray(pos, dtype=np.int32)
@@ -372,6 +420,14 @@ class BaseCounter:
             raise ValueError("read arrays of inconsistent length")
         if n and (cig_off[n] > len(cigar) or seq_off[n] > len(seq) or qual_off[n] > len(qual)):
             raise ValueError("the last offset exceeds its arena")
+        if mapq is not None and (self._quality or flag is None):
+            mapq = np.ascontiguousarray(mapq, dtype=np.uint8)
+            if len(mapq) != n:
+                raise ValueError("read arrays of inconsistent length")
+            check(self._lib.mc_bases_add_batch_mapq(self._h, n, ptr(tid), ptr(pos), ptr(cig_off), ptr(cigar),
+                                                    ptr(l_seq), ptr(seq_off), ptr(seq), ptr(qual_off), ptr(qual),
+                                                    ptr(mapq)), self._lib)
+            return
         if flag is not None:
             flag = np.ascontiguousarray(flag, dtype=np.uint16)
             if len(flag) != n:
@@ -399,6 +455,12 @@ class BaseCounter:
 
         for a in range(0, src.n, int(max_reads)):
             n = min(int(max_reads), src.n - a)
+            if self._quality:
+                check(self._lib.mc_bases_add_batch_device_mapq(
+                    self._h, n, at(tid, a, 4), at(pos, a, 4), at(cig_off, a, 8), at(cigar, 0, 4), src.n_words,
+                    at(l_seq, a, 4), at(seq_off, a, 8), at(seq, 0, 1), src.seq_bytes, at(qual_off, a, 8),
+                    at(qual, 0, 1), src.qual_bytes, at(src._dmapq, a, 1)), self._lib)
+                continue
             if self.strand:
                 check(self._lib.mc_bases_add_batch_device_flags(
                     self._h, n, at(tid, a, 4), at(pos, a, 4), at(cig_off, a, 8), at(cigar, 0, 4), src.n_words,
@@ -409,7 +471,10 @@ class BaseCounter:
                 self._h, n, at(tid, a, 4), at(pos, a, 4), at(cig_off, a, 8), at(cigar, 0, 4), src.n_words,
                 at(l_seq, a, 4), at(seq_off, a, 8), at(seq, 0, 1), src.seq_bytes, at(qual_off, a, 8),
                 at(qual, 0, 1), src.qual_bytes), self._lib)
-        if src.n == 0:       # (the state check of an empty batch, as add_reads makes it)
+        if src.n == 0 and self._quality:
+            check(self._lib.mc_bases_add_batch_device_mapq(self._h, 0, None, None, None, None, 0, None, None, None,
+                                                           0, None, None, 0, None), self._lib)
+        elif src.n == 0:     # (the state check of an empty batch, as add_reads makes it)
             check(self._lib.mc_bases_add_batch_device(self._h, 0, None, None, None, None, 0, None, None, None, 0,
                                                       None, None, 0), self._lib)
 
@@ -431,7 +496,8 @@ class BaseCounter:
                 if b is None:
                     break
                 self.add_reads(b["tid"], b["pos"], b["cig_off"], b["cigar"], b["l_seq"], b["seq_off"], b["seq"],
-                               b["qual_off"], b["qual"], flag=src.flags() if self.strand else None)
+                               b["qual_off"], b["qual"], flag=src.flags() if self.strand else None,
+                               mapq=src.mapq() if self._quality else None)
             return src.counts()
 
     @property
@@ -459,21 +525,46 @@ class BaseCounter:
         check(self._lib.mc_bases_get_reverse(self._h, int(first), int(count), ptr(out)), self._lib)
         return out
 
-    def sites(self, min_depth=1, min_count=1, min_ppm=0, ref=None, min_alt_strand=0):
+    def quality(self, first=0, count=None):
+        """(bq, mq), uint32 [6, count] each over the plane indices of
+        counts(): the sums of the counted bases' quality bytes and of their
+        reads' MAPQ bytes, per channel (bq[DEL] is 0); needs
+        begin(..., quality=True).  A mean is the caller's division by
+        counts()."""
+        if count is None:
+            count = int(self.seg_off[-1]) - int(first)
+        bq = np.zeros((6, max(int(count), 0)), np.uint32)
+        mq = np.zeros((6, max(int(count), 0)), np.uint32)
+        check(self._lib.mc_bases_get_quality(self._h, int(first), int(count), ptr(bq), ptr(mq)), self._lib)
+        return bq, mq
+
+    def sites(self, min_depth=1, min_count=1, min_ppm=0, ref=None, min_alt_strand=0, min_alt_baseq=0,
+              min_alt_mapq=0):
         """The sites among the positions (see the header); ref: optional uint8
         [N], indexed like a plane, 0..3 = A/C/G/T, anything else unknown.
         min_alt_strand (needs begin(..., strand=True)): a site needs one
         alternative allele that passes min_count and min_ppm and is seen this
         many times on each strand.  On a counter that tracks strand the
-        result carries rev_counts."""
+        result carries rev_counts.  min_alt_baseq, min_alt_mapq (0..255, need
+        begin(..., quality=True)): that allele's quality sum reaches
+        min_alt_baseq times its count (DEL exempt) and its MAPQ sum
+        min_alt_mapq times its count.  On a counter that tracks quality the
+        result carries bq_sums and mq_sums."""
         if min_alt_strand and not self.strand:
             raise ValueError("min_alt_strand needs a counter that tracks strand (begin(..., strand=True))")
+        if (min_alt_baseq or min_alt_mapq) and not self._quality:
+            raise ValueError("min_alt_baseq / min_alt_mapq need a counter that tracks quality "
+                             "(begin(..., quality=True))")
         if ref is not None:
             ref = np.ascontiguousarray(ref, dtype=np.uint8)
             if len(ref) != int(self.seg_off[-1]):
                 raise ValueError("the reference plane must have one entry per position")
         n = ctypes.c_int64()
-        if self.strand:
+        if self._quality:
+            check(self._lib.mc_bases_sites_quality(self._h, int(min_depth), int(min_count), int(min_ppm),
+                                                   int(min_alt_baseq), int(min_alt_mapq), ptr(ref),
+                                                   ctypes.byref(n)), self._lib)
+        elif self.strand:
             check(self._lib.mc_bases_sites_strand(self._h, int(min_depth), int(min_count), int(min_ppm),
                                                   int(min_alt_strand), ptr(ref), ctypes.byref(n)), self._lib)
         else:
@@ -489,7 +580,11 @@ class BaseCounter:
         if self.strand:
             rev = np.zeros((n, 6), np.uint32)
             check(self._lib.mc_bases_sites_get_reverse(self._h, 0, n, ptr(rev)), self._lib)
-        return Sites(first, pos, cnt, rev)
+        bq = mq = None
+        if self._quality:
+            bq, mq = np.zeros((n, 6), np.uint32), np.zeros((n, 6), np.uint32)
+            check(self._lib.mc_bases_sites_get_quality(self._h, 0, n, ptr(bq), ptr(mq)), self._lib)
+        return Sites(first, pos, cnt, rev, bq, mq)
 
     def insertions(self, min_depth=1, min_count=1, min_ppm=0):
         """The grouped insertion alleles (see the header, "Insertion alleles")
@@ -527,14 +622,26 @@ class BaseCounter:
                                                    ctypes.byref(n)), self._lib)
         return {"extract_ms": a.value, "group_ms": b.value, "consensus_ms": c.value, "events": n.value}
 
-    def set_counts(self, first, planes, rev=None):
+    def set_counts(self, first, planes, rev=None, bq=None, mq=None):
         """Test hook (mc_bases_set): overwrites plane indices first .. first +
         count with planes, uint32 [6, count]; sites and consensus results are
         gone afterwards.  rev (mc_bases_set_strand, needs strand=True): the
-        reverse planes of the same range, rev <= planes everywhere."""
+        reverse planes of the same range, rev <= planes everywhere.  bq, mq
+        (mc_bases_set_quality, needs quality=True; both or neither): the sum
+        planes of the same range, at most 255 x planes, bq[DEL] zero."""
         planes = np.ascontiguousarray(planes, dtype=np.uint32)
         if planes.ndim != 2 or planes.shape[0] != 6:
             raise ValueError("planes must be [6, count]")
+        if (bq is None) != (mq is None):
+            raise ValueError("bq and mq come together")
+        if bq is not None:
+            bq = np.ascontiguousarray(bq, dtype=np.uint32)
+            mq = np.ascontiguousarray(mq, dtype=np.uint32)
+            if bq.shape != planes.shape or mq.shape != planes.shape:
+                raise ValueError("bq and mq must have the shape of planes")
+            check(self._lib.mc_bases_set_quality(self._h, int(first), planes.shape[1], ptr(planes), ptr(bq),
+                                                 ptr(mq)), self._lib)
+            return
         if rev is not None:
             rev = np.ascontiguousarray(rev, dtype=np.uint32)
             if rev.shape != planes.shape:
@@ -628,6 +735,8 @@ def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, mi
 HEADER = "contig\tpos\tref\tdepth\tA\tC\tG\tT\tN\tDEL\n"
 HEADER_STRAND = (HEADER[:-1] + "".join("\t%s_fwd" % c for c in CHANNELS) +
                  "".join("\t%s_rev" % c for c in CHANNELS) + "\n")
+HEADER_QUALITY = (HEADER[:-1] + "".join("\t%s_bq" % c for c in CHANNELS[:5]) +
+                  "".join("\t%s_mq" % c for c in CHANNELS) + "\n")
 _REF_CODE = np.full(256, 4, np.uint8)
 for _i, _ch in enumerate("ACGT"):
     _REF_CODE[ord(_ch)] = _REF_CODE[ord(_ch.lower())] = _i
@@ -638,13 +747,16 @@ def ref_codes(letters):
     return _REF_CODE[np.asarray(letters, np.uint8)]
 
 
-def write_sites(fh, name, pos, counts, ref=None, rev=None):
+def write_sites(fh, name, pos, counts, ref=None, rev=None, bq=None, mq=None):
     """Tab-separated `contig pos ref depth A C G T N DEL` lines of one contig:
     pos [n] 0-based positions (written 1-based, as mpileup and VCF), counts
     [n, 6], ref [n] uint8 ASCII letters or None ('.').  depth = A + C + G + T
     + DEL.  rev [n, 6] (the reverse-strand share of counts): twelve more
     columns, the six forward counts (counts - rev) and the six reverse ones
-    (HEADER_STRAND).  Returns the lines written."""
+    (HEADER_STRAND).  bq, mq [n, 6] (the quality and MAPQ sums behind counts,
+    both or neither): eleven more columns of exact integer sums, A_bq .. N_bq
+    and A_mq .. DEL_mq (HEADER_QUALITY); a mean is the reader's division by the
+    count.  Returns the lines written."""
     pos = np.asarray(pos, np.int64)
     n = len(pos)
     if n == 0:
@@ -661,6 +773,12 @@ def write_sites(fh, name, pos, counts, ref=None, rev=None):
     if rev is not None:
         rev = np.asarray(rev).reshape(n, 6).astype(np.int64)
         cols += [counts[:, c] - rev[:, c] for c in range(6)] + [rev[:, c] for c in range(6)]
+    if (bq is None) != (mq is None):
+        raise ValueError("bq and mq come together")
+    if bq is not None:
+        bq = np.asarray(bq).reshape(n, 6).astype(np.int64)
+        mq = np.asarray(mq).reshape(n, 6).astype(np.int64)
+        cols += [bq[:, c] for c in range(5)] + [mq[:, c] for c in range(6)]
     for col in cols:
         line = np.char.add(np.char.add(line, "\t"), col.astype(str))
     fh.write("\n".join(line.tolist()))

@@ -37,12 +37,16 @@ Base counts (no counterpart in the reference either):
     python -m metacov_amd.cli bases -b X.bam [-o out.tsv] [-f ref.fa] [-rc R.csv | -rb R.blast7] [--min-baseq 0]
                                     [--min-mapq 0] [--min-depth 1] [--min-count 1] [--min-frac 0.0] [--all]
                                     [--strand [--min-alt-strand 0]]
+                                    [--quality [--min-alt-baseq 0] [--min-alt-mapq 0]]
                                     [--decode host|gpu]
 
 writes `contig pos ref depth A C G T N DEL` for the variant sites, or with
 `--all` for every position, counted on the GPU (metacov_amd/bases.py); one
 process, no read cap, `pos` 1-based.  `--decode gpu` also decodes the BAM on
-the GPU, once, and keeps the records in device memory.
+the GPU, once, and keeps the records in device memory.  `--quality` appends
+the sums of the counted bases' qualities and of their reads' MAPQ per allele
+(`A_bq .. N_bq A_mq .. DEL_mq`) and lets a site ask for an alternative allele
+whose mean qualities reach `--min-alt-baseq` / `--min-alt-mapq`.
 
 Consensus (no counterpart in the reference either):
 
@@ -755,7 +759,7 @@ def _segment_letters(fa, name, start, end):
 
 def write_bases(path, references, tids, starts, ends, outfile, fasta=None, device=0, min_baseq=0, min_mapq=0,
                 min_depth=1, min_count=1, min_ppm=0, every=False, decode="host", insertions=None, strand=False,
-                min_alt_strand=0):
+                min_alt_strand=0, quality=False, min_alt_baseq=0, min_alt_mapq=0):
     """The base-count table of the segments (header contig ids), group by
     group, each written before the next is computed.  decode "host": each
     group is one pass over the BAM on host threads; "gpu": the file is decoded
@@ -764,13 +768,21 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
     thresholds with their own count (`contig pos depth count len seq`).
     strand: twelve more columns, the forward and the reverse counts; a site
     then also needs min_alt_strand reads of an alternative allele on each
-    strand.  Returns (lines written, the source's record counts)."""
+    strand.  quality (not with strand): eleven more columns, the sums of the
+    counted bases' quality bytes and of their reads' MAPQ per allele; a site
+    then also needs an alternative allele whose sums reach min_alt_baseq and
+    min_alt_mapq times its count.  Returns (lines written, the source's record
+    counts)."""
     from . import bases as _bases
     import contextlib
     names = [w.split()[0] if w.split() else w for w in references]
     if min_alt_strand and not strand:
         raise ValueError("min_alt_strand needs strand")
-    outfile.write(_bases.HEADER_STRAND if strand else _bases.HEADER)
+    if (min_alt_baseq or min_alt_mapq) and not quality:
+        raise ValueError("min_alt_baseq / min_alt_mapq need quality")
+    if quality and strand:
+        raise ValueError("quality and strand cannot be combined")
+    outfile.write(_bases.HEADER_STRAND if strand else _bases.HEADER_QUALITY if quality else _bases.HEADER)
     if insertions is not None:
         insertions.write(_bases.INSERTIONS_HEADER)
     written, counts = 0, None
@@ -790,7 +802,7 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
                 raise
         for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
             bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions is not None,
-                     strand=strand)
+                     strand=strand, quality=quality)
             if src is not None:
                 bc.add_device(src)
                 counts = src.counts()
@@ -810,20 +822,25 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
                     for c0 in range(0, n, _bases.GET_CHUNK):
                         c1 = min(n, c0 + _bases.GET_CHUNK)
                         planes = bc.counts(o + c0, c1 - c0)
+                        bq, mq = bc.quality(o + c0, c1 - c0) if quality else (None, None)
                         written += _bases.write_sites(
                             outfile, names[int(tids[i])], np.arange(starts[i] + c0, starts[i] + c1), planes.T,
                             None if letters is None else letters[o + c0:o + c1],
-                            rev=bc.counts_reverse(o + c0, c1 - c0).T if strand else None)
+                            rev=bc.counts_reverse(o + c0, c1 - c0).T if strand else None,
+                            bq=bq.T if quality else None, mq=mq.T if quality else None)
             else:
                 s = bc.sites(min_depth, min_count, min_ppm,
                              ref=None if letters is None else _bases.ref_codes(letters),
-                             min_alt_strand=min_alt_strand)
+                             min_alt_strand=min_alt_strand, min_alt_baseq=min_alt_baseq,
+                             min_alt_mapq=min_alt_mapq)
                 for i in range(a, b):
                     r0, r1 = int(s.first[i - a]), int(s.first[i - a + 1])
                     idx = int(seg_off[i - a]) + (s.pos[r0:r1] - int(starts[i]))
                     written += _bases.write_sites(outfile, names[int(tids[i])], s.pos[r0:r1], s.counts[r0:r1],
                                                   None if letters is None else letters[idx],
-                                                  rev=s.rev_counts[r0:r1] if strand else None)
+                                                  rev=s.rev_counts[r0:r1] if strand else None,
+                                                  bq=s.bq_sums[r0:r1] if quality else None,
+                                                  mq=s.mq_sums[r0:r1] if quality else None)
     return written, counts
 
 
@@ -884,12 +901,22 @@ def _write_insertions(bc, names, tids, starts, seg_off, min_depth, min_count, mi
 @click.option('--min-alt-strand', type=click.IntRange(0), default=0,
               help="A site needs an allele besides the base allele that passes --min-count and --min-frac and "
                    "is seen this many times on each strand (needs --strand)")
+@click.option('--quality', is_flag=True, default=False,
+              help="Also write the evidence behind each count: eleven more columns of exact sums, "
+                   "`A_bq .. N_bq` (quality bytes of the counted bases) and `A_mq .. DEL_mq` (MAPQ of their reads); "
+                   "not with --strand")
+@click.option('--min-alt-baseq', type=click.IntRange(0, 255), default=0,
+              help="A site needs an allele besides the base allele that passes --min-count and --min-frac and "
+                   "whose mean base quality is at least this (a deletion is exempt; needs --quality)")
+@click.option('--min-alt-mapq', type=click.IntRange(0, 255), default=0,
+              help="... and whose reads' mean MAPQ is at least this (needs --quality)")
 @click.option('--device', type=int, default=0, help="HIP device ordinal")
 @click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
               help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
                    "the GPU, the records staying in device memory (the file's reads must fit there)")
 def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regionfile_csv, min_baseq, min_mapq,
-          min_depth, min_count, min_frac, every, strand, min_alt_strand, device, decode):
+          min_depth, min_count, min_frac, every, strand, min_alt_strand, quality, min_alt_baseq, min_alt_mapq, device,
+          decode):
     """
     Write per-position base counts and variant sites
 
@@ -898,7 +925,9 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     else the most frequent allele) passes --min-count and --min-frac at a
     depth of at least --min-depth; with --all every position of the regions.
     --strand adds the counts per strand, --min-alt-strand K keeps the sites
-    whose alternative allele is seen K times on both strands.
+    whose alternative allele is seen K times on both strands.  --quality
+    adds the quality and MAPQ sums per allele, --min-alt-baseq / --min-alt-mapq
+    keep the sites whose alternative allele reaches those means.
     pos is 1-based, as in mpileup and VCF; ref is `.` without -f.  Every
     contig in header order, or the regions of a region file in file order.
     Counted on the GPU; single process only.
@@ -911,6 +940,12 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     min_ppm = int(round(min_frac * 1e6))
     if min_alt_strand and not strand:
         raise click.UsageError("--min-alt-strand needs --strand")
+    if min_alt_baseq and not quality:
+        raise click.UsageError("--min-alt-baseq needs --quality")
+    if min_alt_mapq and not quality:
+        raise click.UsageError("--min-alt-mapq needs --quality")
+    if quality and strand:
+        raise click.UsageError("--quality and --strand cannot be combined")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise click.UsageError("bases runs in one process (WORLD_SIZE > 1 is not supported: "
                                "its output is not sharded)")
@@ -930,7 +965,8 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     n, counts = write_bases(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
                             min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth, min_count=min_count,
                             min_ppm=min_ppm, every=every, decode=decode, insertions=insertions, strand=strand,
-                            min_alt_strand=min_alt_strand)
+                            min_alt_strand=min_alt_strand, quality=quality, min_alt_baseq=min_alt_baseq,
+                            min_alt_mapq=min_alt_mapq)
     outfile.flush()
     if insertions is not None:
         insertions.flush()

@@ -542,8 +542,8 @@ bases_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __res
                   SegBases* __restrict__ resb, const int64_t* __restrict__ out_off,
                   const SegBases* __restrict__ arena, int64_t w_base, int32_t* __restrict__ tid,
                   int32_t* __restrict__ pos, int32_t* __restrict__ l_seq, uint16_t* __restrict__ flag,
-                  int64_t* __restrict__ cig_off, int64_t* __restrict__ seq_off, int64_t* __restrict__ qual_off,
-                  int64_t* __restrict__ src) {
+                  uint8_t* __restrict__ mapq, int64_t* __restrict__ cig_off, int64_t* __restrict__ seq_off,
+                  int64_t* __restrict__ qual_off, int64_t* __restrict__ src) {
     const int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nseg) return;
     int64_t q = seg_off[i];
@@ -610,6 +610,7 @@ bases_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __res
             pos[w] = rb.pos;
             l_seq[w] = rb.l_seq;
             flag[w] = rb.flag;
+            mapq[w] = rb.mapq;
             int64_t* s = src + 3 * (w - w_base);
             s[0] = rb.cig - d;
             s[1] = rb.seq - d;
@@ -782,6 +783,7 @@ struct mc_bam_gpu {
     DBuf<uint32_t> bcigar;                          // CIGAR words
     DBuf<uint8_t> bqual;                            // qualities (the bases are in sseq)
     DBuf<uint16_t> bflag;                           // [n_kept] flag words (the strand is flag & 0x10)
+    DBuf<uint8_t> bmapq;                            // [n_kept] MAPQ bytes (record byte 9)
     int64_t n_words = 0, n_qual = 0;                // arena sizes (the bases': n_bytes)
     int64_t b_passed = 0, b_no_seq = 0, b_bad_cigar = 0;
     DBuf<SegBases> resb, barena;                    // per segment: the count pass, the fill's arena starts
@@ -1070,6 +1072,7 @@ int fill_bases(mc_bam_gpu* g, int64_t n, int64_t nseg, int64_t total) {
     if (int rc = grow(g->pos, need, have)) return rc;
     if (int rc = grow(g->span, need, have)) return rc;
     if (int rc = grow(g->bflag, need, have)) return rc;
+    if (int rc = grow(g->bmapq, need, have)) return rc;
     if (int rc = grow(g->bcig_off, need + 1, have + 1)) return rc;
     if (int rc = grow(g->bseq_off, need + 1, have + 1)) return rc;
     if (int rc = grow(g->bqual_off, need + 1, have + 1)) return rc;
@@ -1091,7 +1094,8 @@ int fill_bases(mc_bam_gpu* g, int64_t n, int64_t nseg, int64_t total) {
         bases_walk_kernel<true><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, 0, nseg, (int32_t)g->hdr.names.size(),
                                                       g->flag_filter, g->min_mapq, g->res.p, g->resb.p, g->out_off.p,
                                                       g->barena.p, g->n_kept, g->tid.p, g->pos.p, g->span.p,
-                                                      g->bflag.p, g->bcig_off.p, g->bseq_off.p, g->bqual_off.p, g->bsrc.p);
+                                                      g->bflag.p, g->bmapq.p, g->bcig_off.p, g->bseq_off.p,
+                                                      g->bqual_off.p, g->bsrc.p);
         HIP_TRY(hipGetLastError());
         constexpr int per_block = 256 / kGatherLanes;
         const int64_t blocks = (total + per_block - 1) / per_block;
@@ -1160,7 +1164,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
             bases_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->flag_filter,
                                                            g->min_mapq, g->res.p, g->resb.p, nullptr, nullptr, 0,
                                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                           nullptr, nullptr);
+                                                           nullptr, nullptr, nullptr);
         else if (g->scan_mode)
             scan_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->res.p, nullptr,
                                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -2480,6 +2484,24 @@ extern "C" int mc_bam_gpu_bases_copy_flags(const mc_bam_gpu* g, uint16_t* flag) 
     if (!g->n_kept) return MC_OK;
     HIP_TRY(hipSetDevice(g->device));
     HIP_TRY(hipMemcpyAsync(flag, g->bflag.p, (size_t)g->n_kept * 2, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bam_gpu_bases_mapq(const mc_bam_gpu* g, const uint8_t** d_mapq) {
+    MC_REQUIRE(g && d_mapq, MC_E_INVALID, "null argument");
+    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    *d_mapq = g->bmapq.p;
+    return MC_OK;
+}
+
+extern "C" int mc_bam_gpu_bases_copy_mapq(const mc_bam_gpu* g, uint8_t* mapq) {
+    MC_REQUIRE(g, MC_E_INVALID, "null argument");
+    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(mapq || !g->n_kept, MC_E_INVALID, "null argument");
+    if (!g->n_kept) return MC_OK;
+    HIP_TRY(hipSetDevice(g->device));
+    HIP_TRY(hipMemcpyAsync(mapq, g->bmapq.p, (size_t)g->n_kept, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return MC_OK;
 }

@@ -43,6 +43,14 @@
 //                         16-bit halves of the same LDS words (two 32-bit
 //                         walks for a tile with more than 65535 reads), the
 //                         flush into the totals and the reverse planes.
+//   bases_pileup_quality_kernel  the same walk on a handle that tracks quality
+//                         (pileup_tile<kModeQuality>): the reads' MAPQ bytes
+//                         beside their other words, one 64-bit LDS add per
+//                         counted base (count, quality byte, MAPQ in 16 + 24 +
+//                         24 bits), kQSub workgroups per tile with kQTile
+//                         8-byte cells each (the same 48 KiB), the reads in
+//                         groups of at most kQGroup with a flush after each
+//                         into the count, bq and mq planes.
 //   bases_ends_kernel     mc_bases_add_batch_device only (the batch is in
 //                         device memory, e.g. the GPU decoder's bases-mode
 //                         table): one thread writes the first and last read's
@@ -66,6 +74,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -86,6 +95,10 @@ constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_runs_compute's boun
 constexpr unsigned long long kNoBad = ~0ull;
 constexpr uint32_t kQueryOps = 0x193u;              // M I S = X advance the query
 constexpr uint32_t kRefOps = 0x18Du;                // M D N = X advance the reference
+constexpr int kModePlain = 0, kModeStrand = 1, kModeQuality = 2;   // what a kernel keeps beside the counts
+constexpr int kQTile = 1024;                        // positions per workgroup of the quality pileup: 48 KiB of cells
+constexpr int kQSub = kTile / kQTile;               // its workgroups per tile, one per kQTile elements of the window
+constexpr int64_t kQGroup = 65535;                  // reads per walk of it: 16-bit count, 24-bit sums, no carry
 
 struct Tile {
     int64_t out;       // plane index of the tile's first position
@@ -183,31 +196,61 @@ __device__ __forceinline__ int64_t lower_bound(const Batch& b, int32_t tid, int6
 // at most once, so neither half can carry); a tile with more reads walks them
 // twice with full 32-bit words, the forward reads first, then the reverse
 // ones.  Both conditions are uniform over the workgroup.
-template <bool kStrand>
+// kQuality: the reads' mapq bytes are read too and every counted base adds
+// one 64-bit LDS word that carries three fields, the count in bits 0..15, the
+// quality byte in bits 16..39 and the read's MAPQ in bits 40..63 (DEL: no
+// quality).  Cells of 8 bytes: a workgroup owns kQTile elements of the tile's
+// window, so the LDS stays 48 KiB and a tile is kQSub workgroups, each with
+// its own binary searches and its own part of the planes.  The reads are
+// walked in groups of at most kQGroup with a flush after each: a read covers a
+// position at most once, so within a group the count stays below 2^16 and both
+// sums below 2^24 and no field carries into the next.  The flush unpacks the
+// fields and adds them into the count, bq and mq planes.
+template <int kMode>
 __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __restrict__ span,
                                             const Tile* __restrict__ tiles, const int32_t* __restrict__ order,
                                             int32_t max_span, int32_t min_baseq, uint32_t* __restrict__ planes,
                                             int64_t stride, const uint16_t* __restrict__ flag,
-                                            uint32_t* __restrict__ rev) {
-    __shared__ __attribute__((aligned(16))) uint32_t acc[kPlanes * kTile];
-    const Tile t = tiles[order[blockIdx.x]];
+                                            uint32_t* __restrict__ rev, const uint8_t* __restrict__ mapq,
+                                            uint32_t* __restrict__ bq, uint32_t* __restrict__ mq) {
+    constexpr bool kStrand = kMode == kModeStrand, kQual = kMode == kModeQuality;
+    constexpr int kW = kQual ? kQTile : kTile;              // elements of the LDS window
+    using Cell = typename std::conditional<kQual, unsigned long long, uint32_t>::type;
+    __shared__ __attribute__((aligned(16))) Cell acc[kPlanes * kW];
+    Tile t = tiles[order[kQual ? blockIdx.x / kQSub : blockIdx.x]];
+    if (kQual) {                                            // this workgroup's part of the tile's window
+        const int w0 = (int)(blockIdx.x % kQSub) * kW;
+        const int a = t.lead > w0 ? t.lead : w0, z = t.lead + t.n < w0 + kW ? t.lead + t.n : w0 + kW;
+        if (a >= z) return;
+        t.out += a - t.lead;
+        t.rel += a - t.lead;
+        t.n = z - a;
+        t.lead = a - w0;                                    // (out - lead stays 16-byte aligned: w0 is a multiple of 4)
+    }
     const int64_t t0 = t.rel, t1 = t.rel + t.n;
     const int64_t lo = lower_bound(b, t.tid, t0 > max_span ? t0 - max_span : 0);
     const int64_t hi = lower_bound(b, t.tid, t1);
     if (lo >= hi) return;
     const bool packed = kStrand && hi - lo <= 65535;
-    const int passes = kStrand && !packed ? 2 : 1;
+    const int passes = kQual ? (int)((hi - lo + kQGroup - 1) / kQGroup) : kStrand && !packed ? 2 : 1;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     for (int pass = 0; pass < passes; ++pass) {
-        if (kStrand && pass) __syncthreads();               // the first pass's flush has read the window
-        for (int k = threadIdx.x * 4; k < kPlanes * kTile; k += kThreads * 4)
-            *reinterpret_cast<uint4*>(&acc[k]) = make_uint4(0, 0, 0, 0);
+        if ((kStrand || kQual) && pass) __syncthreads();    // the pass before has flushed the window
+        if constexpr (kQual) {
+            for (int k = threadIdx.x * 2; k < kPlanes * kW; k += kThreads * 2)
+                *reinterpret_cast<uint4*>(&acc[k]) = make_uint4(0, 0, 0, 0);
+        } else {
+            for (int k = threadIdx.x * 4; k < kPlanes * kTile; k += kThreads * 4)
+                *reinterpret_cast<uint4*>(&acc[k]) = make_uint4(0, 0, 0, 0);
+        }
         __syncthreads();
+        const int64_t glo = kQual ? lo + pass * kQGroup : lo;                          // this pass's reads
+        const int64_t ghi = kQual && glo + kQGroup < hi ? glo + kQGroup : hi;
         // A wave takes 64 consecutive reads at a time: lane i loads read i's words (coalesced, independent
         // loads), then the reads that reach the tile are walked one by one with those words broadcast.
-        for (int64_t g = lo + 64 * (int64_t)wave; g < hi; g += 64 * kWaves) {
+        for (int64_t g = glo + 64 * (int64_t)wave; g < ghi; g += 64 * kWaves) {
             const int64_t mine = g + lane;
-            const bool have = mine < hi;
+            const bool have = mine < ghi;
             const int32_t m_pos = have ? b.pos[mine] : 0;
             const int32_t m_span = have ? span[mine] : 0;
             const int32_t m_l = have ? b.l_seq[mine] : 0;
@@ -217,6 +260,8 @@ __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __res
             const int32_t m_q0 = m_l > 0 ? (int32_t)b.qual[m_qo] : 0;
             int32_t m_rev = 0;
             if (kStrand) m_rev = have ? (int32_t)((flag[mine] >> 4) & 1u) : 0;
+            int32_t m_mq = 0;
+            if (kQual) m_mq = have ? (int32_t)mapq[mine] : 0;
             unsigned long long todo = __ballot(have && (int64_t)m_pos + m_span > t0 &&
                                                (!kStrand || packed || m_rev == pass));
             while (todo) {
@@ -226,8 +271,11 @@ __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __res
                 const int64_t c0 = bcast64(m_c0, i), c1 = bcast64(m_c1, i);
                 const int64_t so = bcast64(m_so, i), qo = bcast64(m_qo, i);
                 const bool test_q = min_baseq > 0 && !(l > 0 && bcast(m_q0, i) == 0xFF);
-                uint32_t one = 1u;
+                bool absent = false;
+                if (kQual) absent = l > 0 && bcast(m_q0, i) == 0xFF;
+                Cell one = 1u;
                 if (kStrand) one = packed && bcast(m_rev, i) ? 0x10000u : 1u;
+                if (kQual) one = (Cell)1u | ((unsigned long long)(uint32_t)bcast(m_mq, i) << 40);
                 int64_t rp = pos, q = 0;
                 for (int64_t k = c0; k < c1 && rp < t1; ++k) {
                     const uint32_t cw = k == c0 ? (uint32_t)bcast((int32_t)m_cw, i) : b.cigar[k];
@@ -240,9 +288,17 @@ __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __res
                             if (qq < l) {
                                 const uint32_t byte = b.seq[so + (qq >> 1)];
                                 const uint32_t code = (qq & 1) ? (byte & 15u) : (byte >> 4);
-                                if (!test_q || (int32_t)b.qual[qo + qq] >= min_baseq) {
+                                if (kQual) {                // the byte is summed too: absent qualities add 0
+                                    const uint32_t qv = absent ? 0u : (uint32_t)b.qual[qo + qq];
+                                    if (!test_q || (int32_t)qv >= min_baseq) {
+                                        const int ch =
+                                            code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : 4;
+                                        atomicAdd(&acc[ch * kW + t.lead + (int)(j - t0)],
+                                                  (Cell)(one + ((unsigned long long)qv << 16)));
+                                    }
+                                } else if (!test_q || (int32_t)b.qual[qo + qq] >= min_baseq) {
                                     const int ch = code == 1 ? 0 : code == 2 ? 1 : code == 4 ? 2 : code == 8 ? 3 : 4;
-                                    atomicAdd(&acc[ch * kTile + t.lead + (int)(j - t0)], one);
+                                    atomicAdd(&acc[ch * kW + t.lead + (int)(j - t0)], one);
                                 }
                             }
                         }
@@ -251,7 +307,7 @@ __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __res
                     } else if (op == 2) {
                         const int64_t e = rp + len < t1 ? rp + len : t1;
                         for (int64_t j = (rp > t0 ? rp : t0) + lane; j < e; j += 64)
-                            atomicAdd(&acc[5 * kTile + t.lead + (int)(j - t0)], one);
+                            atomicAdd(&acc[5 * kW + t.lead + (int)(j - t0)], one);
                         rp += len;
                     } else if (op == 3) {
                         rp += len;
@@ -263,41 +319,82 @@ __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __res
         }
         __syncthreads();
         const int first = t.lead, last = t.lead + t.n;          // the tile's part of the window
+        if constexpr (kQual) {
+            // four cells per thread, the three fields of each into their plane sets (bq of DEL is never added to)
+            for (int e = threadIdx.x * 4; e < kPlanes * kW; e += kThreads * 4) {
+                const int c = e / kW, k = e % kW;
+                const uint4 lo2 = *reinterpret_cast<const uint4*>(&acc[e]);
+                const uint4 hi2 = *reinterpret_cast<const uint4*>(&acc[e + 2]);
+                if (!(lo2.x | lo2.z | hi2.x | hi2.z)) continue;    // (a cell's count is in its low word)
+                const unsigned long long w[4] = {lo2.x | ((unsigned long long)lo2.y << 32),
+                                                 lo2.z | ((unsigned long long)lo2.w << 32),
+                                                 hi2.x | ((unsigned long long)hi2.y << 32),
+                                                 hi2.z | ((unsigned long long)hi2.w << 32)};
+                uint32_t vc[4], vb[4], vm[4];
 #pragma unroll
-        for (int c = 0; c < kPlanes; ++c) {
-            uint32_t* g = planes + c * stride + (t.out - t.lead);   // 16-byte aligned
-            uint32_t* gr = kStrand ? rev + c * stride + (t.out - t.lead) : nullptr;
-            for (int k = threadIdx.x * 4; k < kTile; k += kThreads * 4) {
-                uint4 v = *reinterpret_cast<const uint4*>(&acc[c * kTile + k]);
-                if (!(v.x | v.y | v.z | v.w)) continue;
-                uint4 r = make_uint4(0, 0, 0, 0);               // the reverse strand's share of v
-                if (kStrand) {
-                    if (packed) {
-                        r = make_uint4(v.x >> 16, v.y >> 16, v.z >> 16, v.w >> 16);
-                        v = make_uint4((v.x & 0xFFFFu) + r.x, (v.y & 0xFFFFu) + r.y, (v.z & 0xFFFFu) + r.z,
-                                       (v.w & 0xFFFFu) + r.w);
-                    } else if (pass) {
-                        r = v;
-                    }
+                for (int i = 0; i < 4; ++i) {
+                    vc[i] = (uint32_t)(w[i] & 0xFFFFu);
+                    vb[i] = (uint32_t)(w[i] >> 16) & 0xFFFFFFu;
+                    vm[i] = (uint32_t)(w[i] >> 40);
                 }
+                const int64_t o = c * stride + (t.out - t.lead) + k;   // 16-byte aligned
                 if (k >= first && k + 4 <= last) {
-                    uint4 o = *reinterpret_cast<const uint4*>(g + k);
-                    o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
-                    *reinterpret_cast<uint4*>(g + k) = o;
-                    if (kStrand && (r.x | r.y | r.z | r.w)) {
-                        uint4 p = *reinterpret_cast<const uint4*>(gr + k);
-                        p.x += r.x; p.y += r.y; p.z += r.z; p.w += r.w;
-                        *reinterpret_cast<uint4*>(gr + k) = p;
+                    uint32_t* const dst[3] = {planes + o, bq + o, mq + o};
+                    const uint32_t* const src[3] = {vc, vb, vm};
+#pragma unroll
+                    for (int f = 0; f < 3; ++f) {
+                        if (!(src[f][0] | src[f][1] | src[f][2] | src[f][3])) continue;
+                        uint4 x = *reinterpret_cast<const uint4*>(dst[f]);
+                        x.x += src[f][0]; x.y += src[f][1]; x.z += src[f][2]; x.w += src[f][3];
+                        *reinterpret_cast<uint4*>(dst[f]) = x;
                     }
                 } else {
-                    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
-                    const uint32_t er[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        if (e[i] && k + i >= first && k + i < last) {
-                            g[k + i] += e[i];
-                            if (kStrand && er[i]) gr[k + i] += er[i];
+                        if (vc[i] && k + i >= first && k + i < last) {
+                            planes[o + i] += vc[i];
+                            if (vb[i]) bq[o + i] += vb[i];
+                            if (vm[i]) mq[o + i] += vm[i];
                         }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < kPlanes; ++c) {
+                uint32_t* g = planes + c * stride + (t.out - t.lead);   // 16-byte aligned
+                uint32_t* gr = kStrand ? rev + c * stride + (t.out - t.lead) : nullptr;
+                for (int k = threadIdx.x * 4; k < kTile; k += kThreads * 4) {
+                    uint4 v = *reinterpret_cast<const uint4*>(&acc[c * kTile + k]);
+                    if (!(v.x | v.y | v.z | v.w)) continue;
+                    uint4 r = make_uint4(0, 0, 0, 0);               // the reverse strand's share of v
+                    if (kStrand) {
+                        if (packed) {
+                            r = make_uint4(v.x >> 16, v.y >> 16, v.z >> 16, v.w >> 16);
+                            v = make_uint4((v.x & 0xFFFFu) + r.x, (v.y & 0xFFFFu) + r.y, (v.z & 0xFFFFu) + r.z,
+                                           (v.w & 0xFFFFu) + r.w);
+                        } else if (pass) {
+                            r = v;
+                        }
+                    }
+                    if (k >= first && k + 4 <= last) {
+                        uint4 o = *reinterpret_cast<const uint4*>(g + k);
+                        o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+                        *reinterpret_cast<uint4*>(g + k) = o;
+                        if (kStrand && (r.x | r.y | r.z | r.w)) {
+                            uint4 p = *reinterpret_cast<const uint4*>(gr + k);
+                            p.x += r.x; p.y += r.y; p.z += r.z; p.w += r.w;
+                            *reinterpret_cast<uint4*>(gr + k) = p;
+                        }
+                    } else {
+                        const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+                        const uint32_t er[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (e[i] && k + i >= first && k + i < last) {
+                                g[k + i] += e[i];
+                                if (kStrand && er[i]) gr[k + i] += er[i];
+                            }
+                    }
                 }
             }
         }
@@ -309,7 +406,8 @@ __global__ __launch_bounds__(kThreads) void bases_pileup_kernel(Batch b, const i
                                                                const int32_t* __restrict__ order, int32_t max_span,
                                                                int32_t min_baseq, uint32_t* __restrict__ planes,
                                                                int64_t stride) {
-    pileup_tile<false>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr);
+    pileup_tile<kModePlain>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr, nullptr,
+                            nullptr, nullptr);
 }
 
 // The strand instantiation: flag[n] beside the batch's per-read columns, rev
@@ -321,7 +419,23 @@ __global__ __launch_bounds__(kThreads) void bases_pileup_strand_kernel(Batch b, 
                                                                       uint32_t* __restrict__ planes, int64_t stride,
                                                                       const uint16_t* __restrict__ flag,
                                                                       uint32_t* __restrict__ rev) {
-    pileup_tile<true>(b, span, tiles, order, max_span, min_baseq, planes, stride, flag, rev);
+    pileup_tile<kModeStrand>(b, span, tiles, order, max_span, min_baseq, planes, stride, flag, rev, nullptr, nullptr,
+                         nullptr);
+}
+
+// The quality instantiation: mapq[n] beside the batch's per-read columns, bq
+// and mq the two sum plane sets (indexed like planes); kQSub workgroups per
+// tile.
+__global__ __launch_bounds__(kThreads) void bases_pileup_quality_kernel(Batch b, const int32_t* __restrict__ span,
+                                                                       const Tile* __restrict__ tiles,
+                                                                       const int32_t* __restrict__ order,
+                                                                       int32_t max_span, int32_t min_baseq,
+                                                                       uint32_t* __restrict__ planes, int64_t stride,
+                                                                       const uint8_t* __restrict__ mapq,
+                                                                       uint32_t* __restrict__ bq,
+                                                                       uint32_t* __restrict__ mq) {
+    pileup_tile<kModeQuality>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr, mapq, bq,
+                              mq);
 }
 
 // depth = A + C + G + T + DEL; the base allele is ref (0..3) where given,
@@ -332,10 +446,15 @@ __global__ __launch_bounds__(kThreads) void bases_pileup_strand_kernel(Batch b, 
 // base allele that passes min_count and min_ppm and is seen min_alt times on
 // each strand (r: the reverse counts; forward = total - reverse).  With
 // min_alt == 0 this is the plain predicate: both count tests are monotone in
-// the count, so some allele passes them iff the strongest does.
-template <bool kStrand>
-__device__ __forceinline__ bool is_site(const uint32_t (&a)[5], const uint32_t (&r)[5], int ref, const SiteArgs& s,
-                                        uint32_t min_alt) {
+// the count, so some allele passes them iff the strongest does.  The quality
+// predicate (mc_bases_sites_quality; r: the bq sums, m: the mq sums, min_alt:
+// min_alt_baseq, min_mq: min_alt_mapq): the allele's sums also reach the
+// thresholds times its count, DEL (index 4) with no baseq test; with both 0
+// it is the plain predicate for the same reason.
+template <int kMode>
+__device__ __forceinline__ bool is_site(const uint32_t (&a)[5], const uint32_t (&r)[5], const uint32_t (&m)[5], int ref,
+                                        const SiteArgs& s, uint32_t min_alt, uint32_t min_mq) {
+    constexpr bool kStrand = kMode != kModePlain;
     const unsigned long long depth = (unsigned long long)a[0] + a[1] + a[2] + a[3] + a[4];
     int base = 0;
     if (ref >= 0 && ref < 4) {
@@ -353,6 +472,14 @@ __device__ __forceinline__ bool is_site(const uint32_t (&a)[5], const uint32_t (
         return depth >= s.min_depth && alt >= s.min_count && alt * 1000000ull >= s.min_ppm * depth;
     }
     bool any = false;
+    if (kMode == kModeQuality) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+            any = any || (i != base && a[i] >= s.min_count && a[i] * 1000000ull >= s.min_ppm * depth &&
+                          m[i] >= (unsigned long long)min_mq * a[i] &&
+                          (i == 4 || r[i] >= (unsigned long long)min_alt * a[i]));
+        return depth >= s.min_depth && any;
+    }
 #pragma unroll
     for (int i = 0; i < 5; ++i)
         any = any || (i != base && a[i] >= s.min_count && a[i] * 1000000ull >= s.min_ppm * depth &&
@@ -361,11 +488,14 @@ __device__ __forceinline__ bool is_site(const uint32_t (&a)[5], const uint32_t (
 }
 
 // Bit r of the result: position r * kThreads + threadIdx.x of tile t is a site.
-// rev is read only when kStrand.
-template <bool kStrand>
+// rev (the reverse planes, or the bq planes) is read only when kMode is not
+// kModePlain, mqp (the mq planes) only when it is kModeQuality.
+template <int kMode>
 __device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ planes, const uint32_t* __restrict__ rev,
-                                               int64_t stride, const uint8_t* __restrict__ ref, const Tile& t,
-                                               const SiteArgs& s, uint32_t min_alt) {
+                                               const uint32_t* __restrict__ mqp, int64_t stride,
+                                               const uint8_t* __restrict__ ref, const Tile& t, const SiteArgs& s,
+                                               uint32_t min_alt, uint32_t min_mq) {
+    constexpr bool kStrand = kMode != kModePlain;
     uint32_t fm = 0;
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
@@ -379,7 +509,12 @@ __device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ plan
                 b[0] = rev[i], b[1] = rev[stride + i], b[2] = rev[2 * stride + i], b[3] = rev[3 * stride + i];
                 b[4] = rev[5 * stride + i];
             }
-            fm |= (uint32_t)is_site<kStrand>(a, b, ref ? (int)ref[i] : 4, s, min_alt) << r;
+            uint32_t m[5] = {0, 0, 0, 0, 0};
+            if (kMode == kModeQuality) {
+                m[0] = mqp[i], m[1] = mqp[stride + i], m[2] = mqp[2 * stride + i], m[3] = mqp[3 * stride + i];
+                m[4] = mqp[5 * stride + i];
+            }
+            fm |= (uint32_t)is_site<kMode>(a, b, m, ref ? (int)ref[i] : 4, s, min_alt, min_mq) << r;
         }
     }
     return fm;
@@ -401,12 +536,15 @@ __device__ __forceinline__ void sites_count_tile(uint32_t fm, int32_t* __restric
 }
 
 // The tile's sites from its threads' flag words: positions and counts in
-// position order; site_rev (or null): the reverse counts beside them.
+// position order; site_rev (or null): the reverse counts (or the bq sums)
+// beside them; site_mq (or null): the mq sums.
 __device__ __forceinline__ void sites_emit_tile(uint32_t fm, const Tile& t, const uint32_t* __restrict__ planes,
                                                 const uint32_t* __restrict__ rev, int64_t stride,
                                                 const int64_t* __restrict__ base, int64_t* __restrict__ site_pos,
                                                 uint32_t* __restrict__ site_counts,
-                                                uint32_t* __restrict__ site_rev) {
+                                                uint32_t* __restrict__ site_rev,
+                                                const uint32_t* __restrict__ mqp = nullptr,
+                                                uint32_t* __restrict__ site_mq = nullptr) {
     __shared__ int32_t wcnt[kRounds][kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int32_t rank[kRounds];                                  // sites of this round in lower lanes of the wave
@@ -436,6 +574,10 @@ __device__ __forceinline__ void sites_emit_tile(uint32_t fm, const Tile& t, cons
 #pragma unroll
                 for (int c = 0; c < kPlanes; ++c) site_rev[o * kPlanes + c] = rev[c * stride + i];
             }
+            if (site_mq) {
+#pragma unroll
+                for (int c = 0; c < kPlanes; ++c) site_mq[o * kPlanes + c] = mqp[c * stride + i];
+            }
         }
     }
 }
@@ -448,7 +590,7 @@ __global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* _
                                                               const Tile* __restrict__ tiles, SiteArgs s,
                                                               int32_t* __restrict__ counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags<false>(planes, nullptr, stride, ref, t, s, 0), counts);
+    sites_count_tile(site_flags<kModePlain>(planes, nullptr, nullptr, stride, ref, t, s, 0, 0), counts);
 }
 
 __global__ __launch_bounds__(kThreads) void sites_count_strand_kernel(const uint32_t* __restrict__ planes,
@@ -457,7 +599,7 @@ __global__ __launch_bounds__(kThreads) void sites_count_strand_kernel(const uint
                                                                      const Tile* __restrict__ tiles, SiteArgs s,
                                                                      uint32_t min_alt, int32_t* __restrict__ counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags<true>(planes, rev, stride, ref, t, s, min_alt), counts);
+    sites_count_tile(site_flags<kModeStrand>(planes, rev, nullptr, stride, ref, t, s, min_alt, 0), counts);
 }
 
 // One workgroup.  base[i] = sum of counts[0, i) for i <= n_tiles, then
@@ -480,8 +622,8 @@ __global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __
                                                              int64_t* __restrict__ site_pos,
                                                              uint32_t* __restrict__ site_counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags<false>(planes, nullptr, stride, ref, t, s, 0), t, planes, nullptr, stride, base,
-                    site_pos, site_counts, nullptr);
+    sites_emit_tile(site_flags<kModePlain>(planes, nullptr, nullptr, stride, ref, t, s, 0, 0), t, planes, nullptr,
+                    stride, base, site_pos, site_counts, nullptr);
 }
 
 __global__ __launch_bounds__(kThreads) void sites_emit_strand_kernel(const uint32_t* __restrict__ planes,
@@ -493,8 +635,37 @@ __global__ __launch_bounds__(kThreads) void sites_emit_strand_kernel(const uint3
                                                                     uint32_t* __restrict__ site_counts,
                                                                     uint32_t* __restrict__ site_rev) {
     const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags<true>(planes, rev, stride, ref, t, s, min_alt), t, planes, rev, stride, base,
-                    site_pos, site_counts, site_rev);
+    sites_emit_tile(site_flags<kModeStrand>(planes, rev, nullptr, stride, ref, t, s, min_alt, 0), t, planes, rev,
+                    stride, base, site_pos, site_counts, site_rev);
+}
+
+// The quality kernels of the two passes: the five allele planes of the counts,
+// the bq and the mq sums; the emit also writes the sites' sums.
+__global__ __launch_bounds__(kThreads) void sites_count_quality_kernel(const uint32_t* __restrict__ planes,
+                                                                      const uint32_t* __restrict__ bq,
+                                                                      const uint32_t* __restrict__ mq, int64_t stride,
+                                                                      const uint8_t* __restrict__ ref,
+                                                                      const Tile* __restrict__ tiles, SiteArgs s,
+                                                                      uint32_t min_bq, uint32_t min_mq,
+                                                                      int32_t* __restrict__ counts) {
+    const Tile t = tiles[blockIdx.x];
+    sites_count_tile(site_flags<kModeQuality>(planes, bq, mq, stride, ref, t, s, min_bq, min_mq), counts);
+}
+
+__global__ __launch_bounds__(kThreads) void sites_emit_quality_kernel(const uint32_t* __restrict__ planes,
+                                                                     const uint32_t* __restrict__ bq,
+                                                                     const uint32_t* __restrict__ mq, int64_t stride,
+                                                                     const uint8_t* __restrict__ ref,
+                                                                     const Tile* __restrict__ tiles, SiteArgs s,
+                                                                     uint32_t min_bq, uint32_t min_mq,
+                                                                     const int64_t* __restrict__ base,
+                                                                     int64_t* __restrict__ site_pos,
+                                                                     uint32_t* __restrict__ site_counts,
+                                                                     uint32_t* __restrict__ site_bq,
+                                                                     uint32_t* __restrict__ site_mq) {
+    const Tile t = tiles[blockIdx.x];
+    sites_emit_tile(site_flags<kModeQuality>(planes, bq, mq, stride, ref, t, s, min_bq, min_mq), t, planes, bq, stride,
+                    base, site_pos, site_counts, site_bq, mq, site_mq);
 }
 
 // ---- consensus (the rule is the header's, "Consensus") ----------------------
@@ -746,6 +917,12 @@ struct mc_bases {
     Buf<uint16_t> rflag;                 // the flags of the host batch in flight
     bool have_sites_rev = false;         // the sites are mc_bases_sites_strand's: site_rev is filled
     Buf<uint32_t> site_rev;
+    // quality (opt-in, mc_bases_track_quality): the sums of the counted bases' quality bytes and of their reads' MAPQ
+    bool quality_next = false, quality = false;
+    Buf<uint32_t> bq, mq;                // [6][stride] each, indexed like planes
+    Buf<uint8_t> rmapq;                  // the mapq column of the host batch in flight
+    bool have_sites_q = false;           // the sites are mc_bases_sites_quality's: site_bq and site_mq are filled
+    Buf<uint32_t> site_bq, site_mq;
     ~mc_bases() {
         for (auto& e : iev)
             if (e) (void)hipEventDestroy(e);
@@ -847,6 +1024,9 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(S >= 0 && (S == 0 || (tid && start && end)), MC_E_INVALID, "bad segment arrays");
     MC_REQUIRE(min_baseq >= 0, MC_E_INVALID, "min_baseq %d is negative", min_baseq);
+    MC_REQUIRE(!(h->strand_next && h->quality_next), MC_E_STATE,
+               "strand tracking (mc_bases_track_strand) and quality tracking (mc_bases_track_quality) are both on: "
+               "one handle keeps one of them");
     h->begun = false;
     h->have_sites = false;
     h->have_cons = false;
@@ -854,6 +1034,8 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->tracking = false;
     h->strand = false;
     h->have_sites_rev = false;
+    h->quality = false;
+    h->have_sites_q = false;
 
     // ---- tile table (host): a tile never spans two segments
     std::vector<Tile> tiles;
@@ -910,6 +1092,12 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
         HIP_TRY(h->rev.reserve((size_t)(kPlanes * stride)));
         HIP_TRY(hipMemsetAsync(h->rev.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
     }
+    if (h->quality_next) {
+        HIP_TRY(h->bq.reserve((size_t)(kPlanes * stride)));
+        HIP_TRY(h->mq.reserve((size_t)(kPlanes * stride)));
+        HIP_TRY(hipMemsetAsync(h->bq.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(h->mq.p, 0, (size_t)(kPlanes * stride) * sizeof(uint32_t), st));
+    }
     if (h->track_next) {                          // the events of an earlier begin are gone
         HIP_TRY(h->tile_total.reserve((size_t)T));
         if (T) HIP_TRY(hipMemsetAsync(h->tile_total.p, 0, (size_t)T * 4, st));
@@ -917,6 +1105,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     HIP_TRY(hipStreamSynchronize(st));            // the host vectors are released
     h->tracking = h->track_next;
     h->strand = h->strand_next;
+    h->quality = h->quality_next;
     h->n_events = 0;
     h->ins_from_set = false;
     h->sorted_valid = h->have_weight = false;
@@ -1115,9 +1304,15 @@ __global__ void bases_ends_kernel(Batch b, int32_t* __restrict__ ends) {
 }
 
 // The pileup launch of a batch over tiles [first, first + nt) of the sorted
-// order; flag: the reads' flags in device memory on a handle that tracks strand.
-void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span, const uint16_t* flag) {
-    if (h->strand)
+// order; flag: the reads' flags in device memory on a handle that tracks
+// strand; mapq: their MAPQ bytes there on one that tracks quality.
+void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span, const uint16_t* flag,
+                   const uint8_t* mapq) {
+    if (h->quality)
+        hipLaunchKernelGGL(bases_pileup_quality_kernel, dim3((unsigned)(nt * kQSub)), dim3(kThreads), 0, h->stream, b,
+                           h->span.p, h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride,
+                           mapq, h->bq.p, h->mq.p);
+    else if (h->strand)
         hipLaunchKernelGGL(bases_pileup_strand_kernel, dim3((unsigned)nt), dim3(kThreads), 0, h->stream, b, h->span.p,
                            h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride, flag,
                            h->rev.p);
@@ -1126,17 +1321,29 @@ void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32
                            h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride);
 }
 
-// What every batch entry point checks before it looks at the reads.  flags_fn:
-// the entry point to name to a strand handle's caller who gave no flags;
-// arrays: the per-read arrays other than flag are there.
-int check_batch(const mc_bases* h, int64_t n, bool arrays, bool flagged, const uint16_t* flag, const char* flags_fn) {
+// The per-read column a batch entry point takes beside the nine arrays: none,
+// the flag words (the _flags calls) or the MAPQ bytes (the _mapq calls).
+struct Column {
+    const uint16_t* flag = nullptr;
+    const uint8_t* mapq = nullptr;
+    bool flagged = false, with_mapq = false;
+};
+
+// What every batch entry point checks before it looks at the reads.  device:
+// the device entry points are to be named to a strand or quality handle's
+// caller who gave no flags or no mapq; arrays: the nine per-read arrays are
+// there.
+int check_batch(const mc_bases* h, int64_t n, bool arrays, const Column& col, bool device) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
     MC_REQUIRE(!h->ins_from_set, MC_E_STATE, "insertions were installed by mc_bases_ins_set (call mc_bases_begin)");
-    MC_REQUIRE(flagged || !h->strand, MC_E_STATE, "the handle tracks strand: the reads' flags are needed (%s)",
-               flags_fn);
+    MC_REQUIRE(col.flagged || !h->strand, MC_E_STATE, "the handle tracks strand: the reads' flags are needed (%s)",
+               device ? "mc_bases_add_batch_device_flags" : "mc_bases_add_batch_flags");
+    MC_REQUIRE(col.with_mapq || !h->quality, MC_E_STATE, "the handle tracks quality: the reads' mapq is needed (%s)",
+               device ? "mc_bases_add_batch_device_mapq" : "mc_bases_add_batch_mapq");
     MC_REQUIRE(n >= 0, MC_E_INVALID, "negative read count");
-    MC_REQUIRE(n == 0 || (arrays && (flag || !h->strand)), MC_E_INVALID, "null read arrays");
+    MC_REQUIRE(n == 0 || (arrays && (col.flag || !h->strand) && (col.mapq || !h->quality)), MC_E_INVALID,
+               "null read arrays");
     return MC_OK;
 }
 
@@ -1158,14 +1365,16 @@ int check_order(const mc_bases* h, int32_t tid0, int32_t pos0) {
 }
 
 // A batch from the pre-pass on; b: its arrays in device memory (span has room
-// for its reads), flag: its flags there on a handle that tracks strand.
+// for its reads), flag: its flags there on a handle that tracks strand, mapq:
+// its MAPQ bytes there on one that tracks quality.
 // host_ends: the first and the last read's (tid, pos) where the host has them,
 // else null and bases_ends_kernel fetches them into flags[2..3] (the handle's
 // flags buffer has room for 256 words), one copy back with the pre-pass' words.
 // The order against the previous batch is checked before the pre-pass' verdict.
 // A read the pre-pass rejected: MC_E_INVALID with its index in *bad_read (else
 // -1) and the message left to the caller, who knows where the arrays are.
-int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const uint16_t* flag, int64_t* bad_read) {
+int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const uint16_t* flag, const uint8_t* mapq,
+                 int64_t* bad_read) {
     *bad_read = -1;
     hipStream_t st = h->stream;
     h->pin[0] = kNoBad;
@@ -1206,7 +1415,7 @@ int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const ui
     const auto t_hi = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
                                        std::make_pair(ends[2], (int64_t)ends[3] + max_span));
     if (max_span > 0 && t_lo < t_hi) {
-        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, flag);
+        launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, flag, mapq);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(h->ev[3], st));
@@ -1228,13 +1437,11 @@ int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const ui
     return MC_OK;
 }
 
-// mc_bases_add_batch (flagged false) and mc_bases_add_batch_flags (true).
+// mc_bases_add_batch, mc_bases_add_batch_flags and mc_bases_add_batch_mapq (col: what they take).
 int add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos, const int64_t* cig_off,
               const uint32_t* cigar, const int32_t* l_seq, const int64_t* seq_off, const uint8_t* seq,
-              const int64_t* qual_off, const uint8_t* qual, bool flagged, const uint16_t* flag) {
-    if (int rc = check_batch(h, n, tid && pos && cig_off && l_seq && seq_off && qual_off, flagged, flag,
-                             "mc_bases_add_batch_flags"))
-        return rc;
+              const int64_t* qual_off, const uint8_t* qual, const Column& col) {
+    if (int rc = check_batch(h, n, tid && pos && cig_off && l_seq && seq_off && qual_off, col, false)) return rc;
     if (n == 0) return MC_OK;
     const int64_t n_words = cig_off[n], seq_bytes = seq_off[n], qual_bytes = qual_off[n];
     if (int rc = check_arenas(n_words, cigar, seq_bytes, seq, qual_bytes, qual)) return rc;
@@ -1251,6 +1458,7 @@ int add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos, co
     HIP_TRY(h->seq.reserve((size_t)seq_bytes));
     HIP_TRY(h->qual.reserve((size_t)qual_bytes));
     if (h->strand) HIP_TRY(h->rflag.reserve((size_t)n));
+    if (h->quality) HIP_TRY(h->rmapq.reserve((size_t)n));
     hipStream_t st = h->stream;
     const auto up = [st](void* d, const void* s, size_t bytes) {
         return bytes ? hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
@@ -1264,12 +1472,13 @@ int add_batch(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos, co
     HIP_TRY(up(h->cigar.p, cigar, (size_t)n_words * 4));
     HIP_TRY(up(h->seq.p, seq, (size_t)seq_bytes));
     HIP_TRY(up(h->qual.p, qual, (size_t)qual_bytes));
-    if (h->strand) HIP_TRY(up(h->rflag.p, flag, (size_t)n * 2));
+    if (h->strand) HIP_TRY(up(h->rflag.p, col.flag, (size_t)n * 2));
+    if (h->quality) HIP_TRY(up(h->rmapq.p, col.mapq, (size_t)n));
     const Batch b{h->tid.p, h->pos.p, h->l_seq.p, h->cig_off.p, h->cigar.p, h->seq_off.p, h->seq.p,
                   h->qual_off.p, h->qual.p, n, n_words, seq_bytes, qual_bytes};
     const int32_t ends[4] = {tid[0], pos[0], tid[n - 1], pos[n - 1]};
     int64_t bad = -1;
-    const int rc = finish_batch(h, b, ends, h->rflag.p, &bad);
+    const int rc = finish_batch(h, b, ends, h->rflag.p, h->rmapq.p, &bad);
     if (bad >= 0)
         name_bad_read(h, bad, tid, pos, cig_off, cigar, l_seq, seq_off, qual_off, n_words, seq_bytes, qual_bytes);
     return rc;
@@ -1281,25 +1490,33 @@ extern "C" int mc_bases_add_batch(mc_bases* h, int64_t n, const int32_t* tid, co
                                   const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
                                   const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
                                   const uint8_t* qual) {
-    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, false, nullptr);
+    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, Column{});
 }
 
 extern "C" int mc_bases_add_batch_flags(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
                                         const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
                                         const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
                                         const uint8_t* qual, const uint16_t* flag) {
-    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual, true, flag);
+    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual,
+                     Column{flag, nullptr, true, false});
+}
+
+extern "C" int mc_bases_add_batch_mapq(mc_bases* h, int64_t n, const int32_t* tid, const int32_t* pos,
+                                       const int64_t* cig_off, const uint32_t* cigar, const int32_t* l_seq,
+                                       const int64_t* seq_off, const uint8_t* seq, const int64_t* qual_off,
+                                       const uint8_t* qual, const uint8_t* mapq) {
+    return add_batch(h, n, tid, pos, cig_off, cigar, l_seq, seq_off, seq, qual_off, qual,
+                     Column{nullptr, mapq, false, true});
 }
 
 namespace {
 
-// mc_bases_add_batch_device (flagged false) and mc_bases_add_batch_device_flags (true).
+// mc_bases_add_batch_device, mc_bases_add_batch_device_flags and mc_bases_add_batch_device_mapq.
 int add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos, const int64_t* d_cig_off,
                      const uint32_t* d_cigar, int64_t n_words, const int32_t* d_l_seq, const int64_t* d_seq_off,
                      const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
-                     int64_t qual_bytes, bool flagged, const uint16_t* d_flag) {
-    if (int rc = check_batch(h, n, d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off, flagged, d_flag,
-                             "mc_bases_add_batch_device_flags"))
+                     int64_t qual_bytes, const Column& col) {
+    if (int rc = check_batch(h, n, d_tid && d_pos && d_cig_off && d_l_seq && d_seq_off && d_qual_off, col, true))
         return rc;
     if (n == 0) return MC_OK;
     if (int rc = check_arenas(n_words, d_cigar, seq_bytes, d_seq, qual_bytes, d_qual)) return rc;
@@ -1308,7 +1525,7 @@ int add_batch_device(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t
     const Batch b{d_tid, d_pos, d_l_seq, d_cig_off, d_cigar, d_seq_off, d_seq, d_qual_off, d_qual,
                   n, n_words, seq_bytes, qual_bytes};
     int64_t bad = -1;
-    const int rc = finish_batch(h, b, nullptr, d_flag, &bad);
+    const int rc = finish_batch(h, b, nullptr, col.flag, col.mapq, &bad);
     if (bad < 0) return rc;
     // the bad read's fields behind its predecessor's key (two-entry arrays: name_bad_read's i - 1 and i)
     hipStream_t st = h->stream;
@@ -1350,7 +1567,7 @@ extern "C" int mc_bases_add_batch_device(mc_bases* h, int64_t n, const int32_t* 
                                          int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
                                          int64_t qual_bytes) {
     return add_batch_device(h, n, d_tid, d_pos, d_cig_off, d_cigar, n_words, d_l_seq, d_seq_off, d_seq, seq_bytes,
-                            d_qual_off, d_qual, qual_bytes, false, nullptr);
+                            d_qual_off, d_qual, qual_bytes, Column{});
 }
 
 extern "C" int mc_bases_add_batch_device_flags(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
@@ -1359,7 +1576,16 @@ extern "C" int mc_bases_add_batch_device_flags(mc_bases* h, int64_t n, const int
                                                const uint8_t* d_seq, int64_t seq_bytes, const int64_t* d_qual_off,
                                                const uint8_t* d_qual, int64_t qual_bytes, const uint16_t* d_flag) {
     return add_batch_device(h, n, d_tid, d_pos, d_cig_off, d_cigar, n_words, d_l_seq, d_seq_off, d_seq, seq_bytes,
-                            d_qual_off, d_qual, qual_bytes, true, d_flag);
+                            d_qual_off, d_qual, qual_bytes, Column{d_flag, nullptr, true, false});
+}
+
+extern "C" int mc_bases_add_batch_device_mapq(mc_bases* h, int64_t n, const int32_t* d_tid, const int32_t* d_pos,
+                                              const int64_t* d_cig_off, const uint32_t* d_cigar, int64_t n_words,
+                                              const int32_t* d_l_seq, const int64_t* d_seq_off, const uint8_t* d_seq,
+                                              int64_t seq_bytes, const int64_t* d_qual_off, const uint8_t* d_qual,
+                                              int64_t qual_bytes, const uint8_t* d_mapq) {
+    return add_batch_device(h, n, d_tid, d_pos, d_cig_off, d_cigar, n_words, d_l_seq, d_seq_off, d_seq, seq_bytes,
+                            d_qual_off, d_qual, qual_bytes, Column{nullptr, d_mapq, false, true});
 }
 
 extern "C" int mc_bases_seg_off(const mc_bases* h, int64_t* seg_off) {
@@ -1390,18 +1616,21 @@ extern "C" int mc_bases_device(const mc_bases* h, const uint32_t** d_planes, int
 
 namespace {
 
-// mc_bases_sites (min_alt < 0: the plain predicate and kernels) and
-// mc_bases_sites_strand (min_alt >= 0) share everything but the count and emit
-// launches.
-int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, int64_t min_alt, const uint8_t* ref,
-          int64_t* n_sites) {
-    const bool strand = min_alt >= 0;
+// mc_bases_sites (mode kModePlain: the plain predicate and kernels; min_alt
+// and min_mq unused), mc_bases_sites_strand (kModeStrand, min_alt its
+// threshold) and mc_bases_sites_quality (kModeQuality, min_alt the baseq and
+// min_mq the mapq threshold) share everything but the count and emit launches.
+int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, int mode, int64_t min_alt,
+          int64_t min_mq, const uint8_t* ref, int64_t* n_sites) {
+    const bool strand = mode == kModeStrand, quality = mode == kModeQuality;
     MC_REQUIRE(min_depth >= 0 && min_count >= 0 && min_ppm >= 0 && min_ppm <= 1000000, MC_E_INVALID,
                "site thresholds out of range (min_depth %lld, min_count %lld, min_ppm %lld of 10^6)",
                (long long)min_depth, (long long)min_count, (long long)min_ppm);
     h->have_sites = false;
     h->have_sites_rev = false;
+    h->have_sites_q = false;
     const int64_t T = h->n_tiles, S = h->S;
+    const uint32_t k_mq = (uint32_t)min_mq;
     const uint32_t k_alt = (uint32_t)std::min<int64_t>(std::max<int64_t>(min_alt, 0), UINT32_MAX);
     const SiteArgs sa{(unsigned long long)min_depth, (unsigned long long)min_count, (unsigned long long)min_ppm};
     HIP_TRY(hipSetDevice(h->device));
@@ -1417,7 +1646,10 @@ int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, in
     }
     HIP_TRY(hipEventRecord(h->ev[4], st));
     if (T) {
-        if (strand)
+        if (quality)
+            hipLaunchKernelGGL(sites_count_quality_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
+                               h->bq.p, h->mq.p, h->stride, d_ref, h->tiles.p, sa, k_alt, k_mq, h->counts.p);
+        else if (strand)
             hipLaunchKernelGGL(sites_count_strand_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
                                h->rev.p, h->stride, d_ref, h->tiles.p, sa, k_alt, h->counts.p);
         else
@@ -1434,8 +1666,16 @@ int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, in
     HIP_TRY(h->site_pos.reserve((size_t)total));
     HIP_TRY(h->site_counts.reserve((size_t)total * kPlanes));
     if (strand) HIP_TRY(h->site_rev.reserve((size_t)total * kPlanes));
+    if (quality) {
+        HIP_TRY(h->site_bq.reserve((size_t)total * kPlanes));
+        HIP_TRY(h->site_mq.reserve((size_t)total * kPlanes));
+    }
     if (T) {
-        if (strand)
+        if (quality)
+            hipLaunchKernelGGL(sites_emit_quality_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
+                               h->bq.p, h->mq.p, h->stride, d_ref, h->tiles.p, sa, k_alt, k_mq, h->base.p,
+                               h->site_pos.p, h->site_counts.p, h->site_bq.p, h->site_mq.p);
+        else if (strand)
             hipLaunchKernelGGL(sites_emit_strand_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
                                h->rev.p, h->stride, d_ref, h->tiles.p, sa, k_alt, h->base.p, h->site_pos.p,
                                h->site_counts.p, h->site_rev.p);
@@ -1450,6 +1690,7 @@ int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, in
     h->n_sites = total;
     h->have_sites = true;
     h->have_sites_rev = strand;
+    h->have_sites_q = quality;
     *n_sites = total;
     return MC_OK;
 }
@@ -1460,7 +1701,7 @@ extern "C" int mc_bases_sites(mc_bases* h, int64_t min_depth, int64_t min_count,
                               const uint8_t* ref, int64_t* n_sites) {
     MC_REQUIRE(h && n_sites, MC_E_INVALID, "null argument");
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
-    return sites(h, min_depth, min_count, min_ppm, -1, ref, n_sites);
+    return sites(h, min_depth, min_count, min_ppm, kModePlain, 0, 0, ref, n_sites);
 }
 
 extern "C" int mc_bases_sites_strand(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
@@ -1469,7 +1710,7 @@ extern "C" int mc_bases_sites_strand(mc_bases* h, int64_t min_depth, int64_t min
     MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
     MC_REQUIRE(h->strand, MC_E_STATE, "the handle does not track strand (mc_bases_track_strand before begin)");
     MC_REQUIRE(min_alt_strand >= 0, MC_E_INVALID, "min_alt_strand %lld is negative", (long long)min_alt_strand);
-    return sites(h, min_depth, min_count, min_ppm, min_alt_strand, ref, n_sites);
+    return sites(h, min_depth, min_count, min_ppm, kModeStrand, min_alt_strand, 0, ref, n_sites);
 }
 
 extern "C" int mc_bases_sites_get_reverse(const mc_bases* h, int64_t first, int64_t count, uint32_t* rev_counts) {
@@ -1527,6 +1768,100 @@ extern "C" int mc_bases_set_strand(mc_bases* h, int64_t first, int64_t count, co
     const int rc = mc_bases_set(h, first, count, total);
     if (rc != MC_OK || count == 0) return rc;
     return copy_planes(h, h->rev.p + first, h->stride, rev, count, count, hipMemcpyHostToDevice);
+}
+
+// ---- quality (the header's "Quality sums") -----------------------------------
+
+#define MC_REQUIRE_QUALITY(h) \
+    MC_REQUIRE((h)->quality, MC_E_STATE, "the handle does not track quality (mc_bases_track_quality before begin)")
+
+extern "C" int mc_bases_track_quality(mc_bases* h, int on) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(on == 0 || on == 1, MC_E_INVALID, "on must be 0 or 1, not %d", on);
+    h->quality_next = on != 0;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_get_quality(const mc_bases* h, int64_t first, int64_t count, uint32_t* bq, uint32_t* mq) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE_QUALITY(h);
+    if (int rc = check_range(first, count, h->N, "positions")) return rc;
+    MC_REQUIRE(count == 0 || (bq && mq), MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = copy_planes(h, bq, count, h->bq.p + first, h->stride, count, hipMemcpyDeviceToHost)) return rc;
+    return copy_planes(h, mq, count, h->mq.p + first, h->stride, count, hipMemcpyDeviceToHost);
+}
+
+extern "C" int mc_bases_quality_device(const mc_bases* h, const uint32_t** d_bq, const uint32_t** d_mq,
+                                       int64_t* stride, int64_t* n) {
+    MC_REQUIRE(h && d_bq && d_mq && stride && n, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE_QUALITY(h);
+    *d_bq = h->bq.p;
+    *d_mq = h->mq.p;
+    *stride = h->stride;
+    *n = h->N;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_set_quality(mc_bases* h, int64_t first, int64_t count, const uint32_t* total,
+                                    const uint32_t* bq, const uint32_t* mq) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE_QUALITY(h);
+    if (int rc = check_range(first, count, h->N, "positions")) return rc;
+    MC_REQUIRE(count == 0 || (total && bq && mq), MC_E_INVALID, "null in");
+    for (int64_t k = 0; k < kPlanes * count; ++k) {
+        const long long c = (long long)(k / count), p = (long long)(first + k % count);
+        MC_REQUIRE(bq[k] <= 255ull * total[k], MC_E_INVALID,
+                   "channel %lld, position %lld: baseq sum %u exceeds 255 x count %u", c, p, bq[k], total[k]);
+        MC_REQUIRE(mq[k] <= 255ull * total[k], MC_E_INVALID,
+                   "channel %lld, position %lld: mapq sum %u exceeds 255 x count %u", c, p, mq[k], total[k]);
+        MC_REQUIRE(c != MC_BASES_DEL || bq[k] == 0, MC_E_INVALID,
+                   "position %lld: baseq sum %u of DEL is not 0", p, bq[k]);
+    }
+    const int rc = mc_bases_set(h, first, count, total);
+    if (rc != MC_OK || count == 0) return rc;
+    if (int rc2 = copy_planes(h, h->bq.p + first, h->stride, bq, count, count, hipMemcpyHostToDevice)) return rc2;
+    return copy_planes(h, h->mq.p + first, h->stride, mq, count, count, hipMemcpyHostToDevice);
+}
+
+extern "C" int mc_bases_sites_quality(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                                      int64_t min_alt_baseq, int64_t min_alt_mapq, const uint8_t* ref,
+                                      int64_t* n_sites) {
+    MC_REQUIRE(h && n_sites, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE_QUALITY(h);
+    MC_REQUIRE(min_alt_baseq >= 0 && min_alt_baseq <= 255 && min_alt_mapq >= 0 && min_alt_mapq <= 255, MC_E_INVALID,
+               "quality thresholds outside 0..255 (min_alt_baseq %lld, min_alt_mapq %lld)", (long long)min_alt_baseq,
+               (long long)min_alt_mapq);
+    return sites(h, min_depth, min_count, min_ppm, kModeQuality, min_alt_baseq, min_alt_mapq, ref, n_sites);
+}
+
+extern "C" int mc_bases_sites_get_quality(const mc_bases* h, int64_t first, int64_t count, uint32_t* bq,
+                                          uint32_t* mq) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_sites && h->have_sites_q, MC_E_STATE,
+               "no quality sites computed (call mc_bases_sites_quality)");
+    if (int rc = check_range(first, count, h->n_sites, "sites")) return rc;
+    MC_REQUIRE(count == 0 || (bq && mq), MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(bq, h->site_bq.p + first * kPlanes, (size_t)count * kPlanes * 4, hipMemcpyDeviceToHost,
+                           h->stream));
+    HIP_TRY(hipMemcpyAsync(mq, h->site_mq.p + first * kPlanes, (size_t)count * kPlanes * 4, hipMemcpyDeviceToHost,
+                           h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_quality_dims(int32_t* tile, int32_t* group) {
+    MC_REQUIRE(tile && group, MC_E_INVALID, "null argument");
+    *tile = kQTile;
+    *group = (int32_t)kQGroup;
+    return MC_OK;
 }
 
 extern "C" int mc_bases_sites_first(const mc_bases* h, int64_t* site_first) {

@@ -50,6 +50,7 @@ struct mc_bases_src {
     std::vector<uint32_t> cigar;
     std::vector<uint8_t> seq, qual;
     std::vector<uint16_t> flag;          // (mc_bases_src_flags: the strand is flag & 0x10)
+    std::vector<uint8_t> mapq;           // (mc_bases_src_mapq: the record's MAPQ byte as it is)
     int64_t n_bases = 0;
     ~mc_bases_src() {
         if (prod.joinable()) prod.join();
@@ -59,6 +60,7 @@ struct mc_bases_src {
         pos.clear();
         l_seq.clear();
         flag.clear();
+        mapq.clear();
         cig_off.assign(1, 0);
         seq_off.assign(1, 0);
         qual_off.assign(1, 0);
@@ -205,6 +207,7 @@ int next_batch(mc_bases_src* s, int64_t max_reads, int64_t max_bases) {
         s->pos.push_back(pos);
         s->l_seq.push_back(l_seq);
         s->flag.push_back((uint16_t)flag);
+        s->mapq.push_back((uint8_t)mapq);
         const size_t w0 = s->cigar.size();
         s->cigar.resize(w0 + nc);
         for (uint32_t k = 0; k < nc; ++k) s->cigar[w0 + k] = rd32(cig + 4 * k);
@@ -289,6 +292,12 @@ extern "C" int mc_bases_src_batch(const mc_bases_src* s, const int32_t** tid, co
 extern "C" int mc_bases_src_flags(const mc_bases_src* s, const uint16_t** flag) {
     MC_REQUIRE(s && flag, MC_E_INVALID, "null argument");
     *flag = s->flag.data();
+    return MC_OK;
+}
+
+extern "C" int mc_bases_src_mapq(const mc_bases_src* s, const uint8_t** mapq) {
+    MC_REQUIRE(s && mapq, MC_E_INVALID, "null argument");
+    *mapq = s->mapq.data();
     return MC_OK;
 }
 

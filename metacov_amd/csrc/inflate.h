@@ -840,6 +840,7 @@ struct RecBases {
     const uint8_t* qual;
     bool mapped;
     uint16_t flag;
+    uint8_t mapq;
 };
 
 MC_HD int rec_bases(const uint8_t* r, const uint8_t* rend, int32_t n_ref, uint32_t flag_filter, int32_t min_mapq,
@@ -879,6 +880,7 @@ MC_HD int rec_bases(const uint8_t* r, const uint8_t* rend, int32_t n_ref, uint32
     out.pos = ld_i32(r + 4);
     out.l_seq = l_seq;
     out.flag = (uint16_t)flag;
+    out.mapq = (uint8_t)mapq;
     out.n_cigar = n_cigar;
     out.cig = cig;
     out.seq = seq;
