@@ -14,25 +14,26 @@
 //   K-sync  rec_sync_kernel: one wave per 64 KiB segment of the inflated
 //           stream finds the first offset that starts a chain of 8
 //           structurally valid records (the host decoder's sync_at rule)
-//   K-walk  rec_count_kernel: one lane per segment walks its records from its
-//           start to the next segment's start, counting kept records and
-//           checking each; the host then checks that every walk lands on the
-//           next segment's start (segment 0 starts at the first record, so
-//           consistent segments are exact) and re-walks from the landing
+//   K-walk  walk_kernel<Sink, false>: one lane per segment walks its records
+//           from its start to the next segment's start, counting kept records
+//           and checking each; the host then checks that every walk lands on
+//           the next segment's start (segment 0 starts at the first record,
+//           so consistent segments are exact) and re-walks from the landing
 //           point where a sync was a false positive
-//   K-fill  rec_fill_kernel: the same walk writes the kept (tid, pos, span)
-//           at each segment's offset (file order, as mc_bam_open)
+//   K-fill  walk_kernel<Sink, true>: the same walk writes the kept rows at
+//           each segment's offset (file order, as mc_bam_open)
 //
 // A window's incomplete last record is carried to the front of the next
 // window's inflated buffer.  The kept intervals stay in HBM
 // (mc_bam_gpu_intervals_device) for mc_add_reads_device.
 //
-// Three more modes share the upload, the inflate, the sync and the rounds of
-// parse_window and differ in the walk: scan mode (scan_walk_kernel: every
-// record as scan's SoA batch), reads mode (reads_walk_kernel: the placed
-// records as pileup.experimental's read table) and bases mode
-// (bases_walk_kernel + bases_gather_kernel: the base counter's records with
-// CIGAR, SEQ and QUAL in three arenas, mc_bases_add_batch's layout).
+// The four modes share the upload, the inflate, the sync, the walk's frame
+// and the rounds of parse_window, and differ in the walk's sink: intervals
+// mode (IntervalsSink: the kept tid, pos, span), scan mode (ScanSink: every
+// record as scan's SoA batch), reads mode (ReadsSink: the placed records as
+// pileup.experimental's read table) and bases mode (BasesSink +
+// bases_gather_kernel: the base counter's records with CIGAR, SEQ and QUAL
+// in three arenas, mc_bases_add_batch's layout).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -166,204 +167,176 @@ struct ExtAcc {
     unsigned long long nfirst, end, mapped, unmapped, kept;
 };
 
-// One lane per segment: walk [seg_off[i], seg_off[i+1]) (kFill: write the
-// kept intervals at out_off[i]).  The walk of a segment ends at the first
-// record boundary >= seg_off[i+1], at an incomplete record, or at an error.
+// The record walk is one frame (walk_kernel) and one sink per mode.  The
+// frame owns what parse_window's rounds depend on: one lane per segment walks
+// [seg_off[i], seg_off[i+1]) record by record, checks each record's framing,
+// and ends at the first record boundary >= seg_off[i+1], at an incomplete
+// record, or at an error; a count pass (!kFill) leaves the segment's SegRes, a
+// fill (kFill) writes rows [out_off[i], + res[i].kept) and never more than
+// that count pass sized.  A sink reads what its mode takes of a framed record
+// and, in a fill, writes its columns.
+struct WalkArgs {
+    const uint8_t* d;          // the inflated stream d[0, n)
+    int64_t n;
+    const int64_t* seg_off;    // [nseg + 1] segment starts
+    int64_t first, nseg;       // the lanes take segments [first, nseg)
+    int32_t n_ref;
+    SegRes* res;               // count pass: written; fill: res[i].kept bounds segment i's rows
+    const int64_t* out_off;    // fill: each segment's first row
+    const int64_t* byte_off;   // fill, sinks with a byte arena (kArena): each segment's first arena byte
+};
+
+// What a sink reports of one framed record.  err without err_after: the record
+// is refused where it starts (err_at = its offset, not counted); with
+// err_after: it is counted and the walk moves past it first (err_at = the
+// offset after it).  wrote: the fill wrote row w (and `bytes` of the arena).
+struct Step {
+    int32_t err = 0;
+    bool err_after = false;
+    bool mapped = false, kept = false, wrote = false;
+    int64_t bytes = 0;
+};
+
+// Bytes [k, k + 4) of a byte-aligned source of nbytes bytes as one dword, zero
+// past its end.
+__device__ __forceinline__ uint32_t ld_dword_within(const uint8_t* src, int64_t k, int64_t nbytes) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (k + e < nbytes) v |= (uint32_t)src[k + e] << (8 * e);
+    return v;
+}
+
+// Intervals mode: the kept (tid, pos, span), file order, as mc_bam_open.
 // tid_map (optional, a contig-subset decode): a kept record's tid becomes
 // tid_map[tid], and a record whose entry is negative is not kept.  ext
 // (kFill, optional): the per-contig table, offsets plus `base` (the stream
 // offset of d[0]), one set of atomics per run of one contig in a segment.
-template <bool kFill>
-__global__ void __launch_bounds__(256)
-rec_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __restrict__ seg_off, int64_t first,
-                int64_t nseg, int32_t n_ref, uint32_t flag_filter, SegRes* __restrict__ res,
-                const int64_t* __restrict__ out_off, int32_t* __restrict__ tid, int32_t* __restrict__ pos,
-                int32_t* __restrict__ span, const int32_t* __restrict__ tid_map, ExtAcc* __restrict__ ext,
-                int64_t base) {
-    const int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nseg) return;
-    int64_t q = seg_off[i];
-    const int64_t end = seg_off[i + 1];
-    int64_t records = 0, mapped = 0, kept = 0, err_at = 0;
-    int32_t err = 0;
-    int64_t w = 0, w_end = 0;
-    if (kFill) {
-        w = out_off[i];
-        w_end = w + res[i].kept;
-    }
+struct IntervalsSink {
+    struct Args {
+        uint32_t flag_filter;
+        const int32_t* tid_map;
+        int32_t *tid, *pos, *span;
+        ExtAcc* ext;
+        int64_t base;
+    };
+    static constexpr bool kArena = false;
     // the current run of one contig (ext)
     int32_t run_t = -2;
     int64_t run_q0 = 0, run_q1 = 0;
     unsigned long long run_m = 0, run_u = 0, run_k = 0;
-    auto flush = [&]() {
+
+    __device__ __forceinline__ void flush(const WalkArgs& a, const Args& s) {
         if (run_t < -1) return;
-        ExtAcc* e = ext + (run_t < 0 ? n_ref : run_t);
-        atomicMax(&e->nfirst, ~(unsigned long long)(base + run_q0));
-        atomicMax(&e->end, (unsigned long long)(base + run_q1));
+        ExtAcc* e = s.ext + (run_t < 0 ? a.n_ref : run_t);
+        atomicMax(&e->nfirst, ~(unsigned long long)(s.base + run_q0));
+        atomicMax(&e->end, (unsigned long long)(s.base + run_q1));
         if (run_m) atomicAdd(&e->mapped, run_m);
         if (run_u) atomicAdd(&e->unmapped, run_u);
         if (run_k) atomicAdd(&e->kept, run_k);
-    };
-    while (q < end) {
-        if (q + 4 > n) {
-            err = kSegIncomplete;
-            break;
-        }
-        const int32_t bs = mc::gz::ld_i32(d + q);
-        if (bs < 32) {
-            err = kSegBadSize;
-            err_at = q;
-            break;
-        }
-        if (q + 4 + (int64_t)bs > n) {
-            err = kSegIncomplete;
-            break;
-        }
-        const uint8_t* r = d + q + 4;
+    }
+    template <bool kFill>
+    __device__ __forceinline__ void begin(const WalkArgs&, const Args&, int64_t) {}
+    template <bool kFill>
+    __device__ __forceinline__ Step record(const WalkArgs& a, const Args& s, const uint8_t* r, int32_t bs, int64_t q0,
+                                           int64_t w, int64_t, bool room) {
+        Step st;
         mc::gz::RecOut ro;
-        int rc = mc::gz::rec_parse(r, r + bs, n_ref, flag_filter, ro);
-        const int64_t q0 = q;
-        q += 4 + (int64_t)bs;
-        ++records;
-        mapped += ro.mapped ? 1 : 0;
+        int rc = mc::gz::rec_parse(r, r + bs, a.n_ref, s.flag_filter, ro);
+        st.mapped = ro.mapped;
         if (rc >= 2) {
-            err = rc == 2 ? kSegTid : rc == 3 ? kSegCigar : kSegSpan;
-            err_at = q;
-            break;
+            st.err = rc == 2 ? kSegTid : rc == 3 ? kSegCigar : kSegSpan;
+            st.err_after = true;
+            return st;
         }
         const int32_t raw_t = mc::gz::ld_i32(r);
-        if (rc == 1 && tid_map) {
-            const int32_t lt = tid_map[ro.tid];
+        if (rc == 1 && s.tid_map) {
+            const int32_t lt = s.tid_map[ro.tid];
             if (lt < 0) rc = 0;
             ro.tid = lt;
         }
-        if (kFill && ext && raw_t >= -1 && raw_t < n_ref) {
+        if (kFill && s.ext && raw_t >= -1 && raw_t < a.n_ref) {
             if (raw_t != run_t) {
-                flush();
+                flush(a, s);
                 run_t = raw_t;
                 run_q0 = q0;
                 run_m = run_u = run_k = 0;
             }
-            run_q1 = q;
-            if (raw_t >= 0 && !(mc::gz::ld_u16(r + 14) & 4u)) ++run_m;
-            else ++run_u;
-            if (rc == 1) ++run_k;
+            run_q1 = q0 + 4 + (int64_t)bs;
+            // ro.mapped is rec_parse's "tid >= 0 and not flagged unmapped" of this record: no second
+            // load of the flag.  (Sums, not branches to one counter or the other: the three stay in
+            // registers.)
+            run_m += ro.mapped ? 1 : 0;
+            run_u += ro.mapped ? 0 : 1;
+            run_k += rc == 1 ? 1 : 0;
         }
         if (rc == 1) {
-            if (kFill && w < w_end) {
-                tid[w] = ro.tid;
-                pos[w] = ro.pos;
-                span[w] = ro.span;
-                ++w;
+            st.kept = true;
+            if (kFill && room) {
+                s.tid[w] = ro.tid;
+                s.pos[w] = ro.pos;
+                s.span[w] = ro.span;
+                st.wrote = true;
             }
-            ++kept;
         }
+        return st;
     }
-    if (kFill && ext) flush();
-    if (!kFill) {
-        SegRes s;
-        s.landing = q;
-        s.records = records;
-        s.mapped = mapped;
-        s.kept = kept;
-        s.err_at = err_at;
-        s.bytes = 0;
-        s.err = err;
-        s.pad = 0;
-        res[i] = s;
+    template <bool kFill>
+    __device__ __forceinline__ void end(const WalkArgs& a, const Args& s, int64_t) {
+        if (kFill && s.ext) flush(a, s);
     }
-}
+};
 
 // Scan mode (`metacov scan` on BAM input, scan_src.cpp's bam_next on the
 // device): every record is kept, in file order, as the SoA batch the scan
 // kernels take: rlen (l_seq), flag, gpos (pos + l_seq on the reverse strand),
 // gisize (tlen when properly paired, else 0), tid, and its packed nt16 bases
 // at a 4-byte aligned offset (seq_off[k + 1] = the aligned end of record k).
-// One lane per segment, as rec_walk_kernel.
-template <bool kFill>
-__global__ void __launch_bounds__(256)
-scan_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __restrict__ seg_off, int64_t first,
-                 int64_t nseg, int32_t n_ref, SegRes* __restrict__ res, const int64_t* __restrict__ out_off,
-                 const int64_t* __restrict__ byte_off, int32_t* __restrict__ rlen, int32_t* __restrict__ flag,
-                 int32_t* __restrict__ gpos, int32_t* __restrict__ gisize, int32_t* __restrict__ tid,
-                 int64_t* __restrict__ seq_off, uint8_t* __restrict__ seq) {
-    const int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nseg) return;
-    int64_t q = seg_off[i];
-    const int64_t end = seg_off[i + 1];
-    int64_t records = 0, mapped = 0, bytes = 0, err_at = 0;
-    int32_t err = 0;
-    int64_t w = 0, w_end = 0, b = 0;
-    if (kFill) {
-        w = out_off[i];
-        w_end = w + res[i].kept;
-        b = byte_off[i];
-    }
-    while (q < end) {
-        if (q + 4 > n) {
-            err = kSegIncomplete;
-            break;
-        }
-        const int32_t bs = mc::gz::ld_i32(d + q);
-        if (bs < 32) {
-            err = kSegBadSize;
-            err_at = q;
-            break;
-        }
-        if (q + 4 + (int64_t)bs > n) {
-            err = kSegIncomplete;
-            break;
-        }
-        const uint8_t* r = d + q + 4;
+struct ScanSink {
+    struct Args {
+        int32_t *rlen, *flag, *gpos, *gisize, *tid;
+        int64_t* seq_off;
+        uint8_t* seq;
+    };
+    static constexpr bool kArena = true;
+
+    template <bool kFill>
+    __device__ __forceinline__ void begin(const WalkArgs&, const Args&, int64_t) {}
+    template <bool kFill>
+    __device__ __forceinline__ Step record(const WalkArgs& a, const Args& s, const uint8_t* r, int32_t bs, int64_t,
+                                           int64_t w, int64_t b, bool room) {
+        Step st;
         const int32_t t = mc::gz::ld_i32(r), pos = mc::gz::ld_i32(r + 4);
         const uint32_t l_name = r[8], n_cigar = mc::gz::ld_u16(r + 12), fl = mc::gz::ld_u16(r + 14);
         const int32_t l_seq = mc::gz::ld_i32(r + 16), tlen = mc::gz::ld_i32(r + 28);
         const int64_t seq_at = 32 + (int64_t)l_name + 4 * (int64_t)n_cigar;
         const int64_t nbytes = ((int64_t)(l_seq > 0 ? l_seq : 0) + 1) / 2;
-        if (l_seq < 0 || seq_at + nbytes > bs || t < -1 || t >= n_ref) {
-            err = kSegMalformed;
-            err_at = q;
-            break;
+        if (l_seq < 0 || seq_at + nbytes > bs || t < -1 || t >= a.n_ref) {
+            st.err = kSegMalformed;
+            return st;
         }
-        q += 4 + (int64_t)bs;
-        ++records;
-        mapped += (t >= 0 && !(fl & 4u)) ? 1 : 0;
+        st.mapped = t >= 0 && !(fl & 4u);
+        st.kept = true;
         const int64_t al = (nbytes + 3) & ~(int64_t)3;
-        bytes += al;
-        if (kFill && w < w_end) {
-            rlen[w] = l_seq;
-            flag[w] = (int32_t)fl;
-            gpos[w] = (fl & 0x10u) ? pos + l_seq : pos;
-            gisize[w] = (fl & 0x2u) ? tlen : 0;
-            tid[w] = t;
+        st.bytes = al;
+        if (kFill && room) {
+            s.rlen[w] = l_seq;
+            s.flag[w] = (int32_t)fl;
+            s.gpos[w] = (fl & 0x10u) ? pos + l_seq : pos;
+            s.gisize[w] = (fl & 0x2u) ? tlen : 0;
+            s.tid[w] = t;
             // the bases, dword by dword (the source is byte-aligned)
             const uint8_t* src = r + seq_at;
-            uint32_t* dst = reinterpret_cast<uint32_t*>(seq + b);
-            for (int64_t k = 0; k < al; k += 4) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (k + e < nbytes) v |= (uint32_t)src[k + e] << (8 * e);
-                dst[k >> 2] = v;
-            }
-            b += al;
-            seq_off[w + 1] = b;
-            ++w;
+            uint32_t* dst = reinterpret_cast<uint32_t*>(s.seq + b);
+            for (int64_t k = 0; k < al; k += 4) dst[k >> 2] = ld_dword_within(src, k, nbytes);
+            s.seq_off[w + 1] = b + al;
+            st.wrote = true;
         }
+        return st;
     }
-    if (!kFill) {
-        SegRes s;
-        s.landing = q;
-        s.records = records;
-        s.mapped = mapped;
-        s.kept = records;
-        s.err_at = err_at;
-        s.bytes = bytes;
-        s.err = err;
-        s.pad = 0;
-        res[i] = s;
-    }
-}
+    template <bool kFill>
+    __device__ __forceinline__ void end(const WalkArgs&, const Args&, int64_t) {}
+};
 
 // Reads mode (pileup.experimental's read table, exp_reads.cpp's walk on the
 // device): every placed record (tid >= 0) in file order with what
@@ -371,8 +344,8 @@ scan_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __rest
 // when unmapped or 0), flag, bits (1: no SEQ, 2: no reference length), the
 // 2-bit code of the first k bases of query_alignment_sequence (0xFFFFFFFF:
 // none), and its name (NUL-free bytes, name_off[w] into the names arena).
-// One lane per segment, as rec_walk_kernel.  tid_map (a contig-subset
-// decode): only records whose entry is >= 0 are taken; tids stay the header's.
+// tid_map (a contig-subset decode): only records whose entry is >= 0 are
+// taken; tids stay the header's.
 __device__ __forceinline__ uint32_t exp_kmer(const uint8_t* cig, uint32_t n_cigar, const uint8_t* seq, int32_t l_seq,
                                              int k) {
     int64_t qs = 0, qe = l_seq;
@@ -406,115 +379,86 @@ __device__ __forceinline__ uint32_t exp_kmer(const uint8_t* cig, uint32_t n_ciga
     return code;
 }
 
-template <bool kFill>
-__global__ void __launch_bounds__(256)
-reads_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __restrict__ seg_off, int64_t first,
-                  int64_t nseg, int32_t n_ref, int k, SegRes* __restrict__ res, const int64_t* __restrict__ out_off,
-                  const int64_t* __restrict__ byte_off, int32_t* __restrict__ tid, int32_t* __restrict__ pos,
-                  int64_t* __restrict__ end_pos, int32_t* __restrict__ flag, uint8_t* __restrict__ bits,
-                  uint32_t* __restrict__ kmer, uint8_t* __restrict__ name_len, int64_t* __restrict__ name_off,
-                  uint8_t* __restrict__ names, const int32_t* __restrict__ tid_map) {
-    const int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nseg) return;
-    int64_t q = seg_off[i];
-    const int64_t end = seg_off[i + 1];
-    int64_t records = 0, mapped = 0, placed = 0, bytes = 0, err_at = 0;
-    int32_t err = 0;
-    int64_t w = 0, w_end = 0, b = 0;
-    if (kFill) {
-        w = out_off[i];
-        w_end = w + res[i].kept;
-        b = byte_off[i];
-    }
-    while (q < end) {
-        if (q + 4 > n) {
-            err = kSegIncomplete;
-            break;
-        }
-        const int32_t bs = mc::gz::ld_i32(d + q);
-        if (bs < 32) {
-            err = kSegBadSize;
-            err_at = q;
-            break;
-        }
-        if (q + 4 + (int64_t)bs > n) {
-            err = kSegIncomplete;
-            break;
-        }
-        const uint8_t* r = d + q + 4;
+struct ReadsSink {
+    struct Args {
+        int k;
+        const int32_t* tid_map;
+        int32_t *tid, *pos;
+        int64_t* end_pos;
+        int32_t* flag;
+        uint8_t* bits;
+        uint32_t* kmer;
+        uint8_t* name_len;
+        int64_t* name_off;
+        uint8_t* names;
+    };
+    static constexpr bool kArena = true;
+
+    template <bool kFill>
+    __device__ __forceinline__ void begin(const WalkArgs&, const Args&, int64_t) {}
+    template <bool kFill>
+    __device__ __forceinline__ Step record(const WalkArgs& a, const Args& s, const uint8_t* r, int32_t bs, int64_t,
+                                           int64_t w, int64_t b, bool room) {
+        Step st;
         const uint8_t* rend = r + bs;
         const int32_t t = mc::gz::ld_i32(r);
         const uint32_t l_name = r[8], fl = mc::gz::ld_u16(r + 14);
         const int32_t l_seq = mc::gz::ld_i32(r + 16);
-        if (t < -1 || t >= n_ref || l_name == 0 || l_seq < 0) {
-            err = kSegMalformed;
-            err_at = q;
-            break;
+        if (t < -1 || t >= a.n_ref || l_name == 0 || l_seq < 0) {
+            st.err = kSegMalformed;
+            return st;
         }
-        if (t >= 0 && (!tid_map || tid_map[t] >= 0)) {   // (a contig-subset decode: the selected contigs)
-            uint32_t n_cigar = mc::gz::ld_u16(r + 12);
-            const uint8_t* cig = r + 32 + l_name;
-            const uint8_t* seq = cig + 4ull * n_cigar;
-            bool ok = cig + 4ull * n_cigar <= rend && seq + ((uint64_t)l_seq + 1) / 2 <= rend;
-            if (ok && n_cigar == 2 && mc::gz::ld_u32(cig) == (((uint32_t)l_seq << 4) | 4u) &&
-                (mc::gz::ld_u32(cig + 4) & 0xFu) == 3u) {   // the CG:B,I placeholder
-                const uint8_t* aux = seq + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
-                const uint8_t* words = nullptr;
-                uint32_t cnt = 0;
-                if (aux <= rend && mc::gz::find_cg(aux, rend, &words, &cnt) && words) {
-                    cig = words;
-                    n_cigar = cnt;
+        // only placed records (a contig-subset decode: of the selected contigs) are taken
+        if (!(t >= 0 && (!s.tid_map || s.tid_map[t] >= 0))) return st;
+        uint32_t n_cigar = mc::gz::ld_u16(r + 12);
+        const uint8_t* cig = r + 32 + l_name;
+        const uint8_t* seq = cig + 4ull * n_cigar;
+        const bool ok = cig + 4ull * n_cigar <= rend && seq + ((uint64_t)l_seq + 1) / 2 <= rend;
+        if (ok && n_cigar == 2 && mc::gz::ld_u32(cig) == (((uint32_t)l_seq << 4) | 4u) &&
+            (mc::gz::ld_u32(cig + 4) & 0xFu) == 3u) {   // the CG:B,I placeholder
+            const uint8_t* aux = seq + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq;
+            const uint8_t* words = nullptr;
+            uint32_t cnt = 0;
+            if (aux <= rend && mc::gz::find_cg(aux, rend, &words, &cnt) && words) {
+                cig = words;
+                n_cigar = cnt;
+            }
+        }
+        if (!ok) {
+            st.err = kSegMalformed;
+            return st;
+        }
+        uint32_t nl = 0;
+        while (nl < l_name && r[32 + nl]) ++nl;
+        if (kFill && room) {
+            const bool unmapped = fl & 4u;
+            int64_t rlen = 0;
+            if (!unmapped)
+                for (uint32_t c = 0; c < n_cigar; ++c) {
+                    const uint32_t cw = mc::gz::ld_u32(cig + 4ull * c);
+                    if ((0x18Du >> (cw & 0xFu)) & 1u) rlen += cw >> 4;
                 }
-            }
-            if (!ok) {
-                err = kSegMalformed;
-                err_at = q;
-                break;
-            }
-            uint32_t nl = 0;
-            while (nl < l_name && r[32 + nl]) ++nl;
-            if (kFill && w < w_end) {
-                const bool unmapped = fl & 4u;
-                int64_t rlen = 0;
-                if (!unmapped)
-                    for (uint32_t c = 0; c < n_cigar; ++c) {
-                        const uint32_t cw = mc::gz::ld_u32(cig + 4ull * c);
-                        if ((0x18Du >> (cw & 0xFu)) & 1u) rlen += cw >> 4;
-                    }
-                if (rlen == 0) rlen = 1;
-                const int32_t p = mc::gz::ld_i32(r + 4);
-                tid[w] = t;
-                pos[w] = p;
-                end_pos[w] = (int64_t)p + rlen;
-                flag[w] = (int32_t)fl;
-                bits[w] = (uint8_t)((l_seq == 0 ? 1 : 0) | ((unmapped || n_cigar == 0) ? 2 : 0));
-                kmer[w] = l_seq ? exp_kmer(cig, n_cigar, seq, l_seq, k) : 0xFFFFFFFFu;
-                name_len[w] = (uint8_t)nl;
-                name_off[w] = b;
-                for (uint32_t c = 0; c < nl; ++c) names[b + c] = r[32 + c];
-                b += nl;
-                ++w;
-            }
-            ++placed;
-            bytes += nl;
-            mapped += (fl & 4u) ? 0 : 1;
+            if (rlen == 0) rlen = 1;
+            const int32_t p = mc::gz::ld_i32(r + 4);
+            s.tid[w] = t;
+            s.pos[w] = p;
+            s.end_pos[w] = (int64_t)p + rlen;
+            s.flag[w] = (int32_t)fl;
+            s.bits[w] = (uint8_t)((l_seq == 0 ? 1 : 0) | ((unmapped || n_cigar == 0) ? 2 : 0));
+            s.kmer[w] = l_seq ? exp_kmer(cig, n_cigar, seq, l_seq, s.k) : 0xFFFFFFFFu;
+            s.name_len[w] = (uint8_t)nl;
+            s.name_off[w] = b;
+            for (uint32_t c = 0; c < nl; ++c) s.names[b + c] = r[32 + c];
+            st.wrote = true;
         }
-        q += 4 + (int64_t)bs;
-        ++records;
+        st.kept = true;
+        st.bytes = nl;
+        st.mapped = !(fl & 4u);
+        return st;
     }
-    if (!kFill) {
-        SegRes s;
-        s.landing = q;
-        s.records = records;
-        s.mapped = mapped;
-        s.kept = placed;
-        s.err_at = err_at;
-        s.bytes = bytes;
-        s.err = err;
-        s.pad = 0;
-        res[i] = s;
-    }
-}
+    template <bool kFill>
+    __device__ __forceinline__ void end(const WalkArgs&, const Args&, int64_t) {}
+};
 
 // Bases mode (the base counter's input, bases_src.cpp's next_batch on the
 // device): the records mc::gz::rec_bases takes, in file order, as
@@ -529,113 +473,162 @@ struct SegBases {
     int64_t words, seq_bytes, qual_bytes;   // arena sizes of the records taken (seq_bytes: each rounded up to 4)
 };
 
-// One lane per segment, as rec_walk_kernel.  kFill: read w of the table gets
-// its columns, the ends of its three arena ranges (the offsets of read w + 1)
-// and the offsets of its CIGAR, SEQ and QUAL in the inflated stream
-// (src[3 * (w - w_base) ..]) for bases_gather_kernel; a lane writes only
-// reads [out_off[i], + res[i].kept) and only while its arena ranges stay
-// inside the sizes its count pass gave (arena[i]).
-template <bool kFill>
-__global__ void __launch_bounds__(256)
-bases_walk_kernel(const uint8_t* __restrict__ d, int64_t n, const int64_t* __restrict__ seg_off, int64_t first,
-                  int64_t nseg, int32_t n_ref, uint32_t flag_filter, int32_t min_mapq, SegRes* __restrict__ res,
-                  SegBases* __restrict__ resb, const int64_t* __restrict__ out_off,
-                  const SegBases* __restrict__ arena, int64_t w_base, int32_t* __restrict__ tid,
-                  int32_t* __restrict__ pos, int32_t* __restrict__ l_seq, uint16_t* __restrict__ flag,
-                  uint8_t* __restrict__ mapq, int64_t* __restrict__ cig_off, int64_t* __restrict__ seq_off,
-                  int64_t* __restrict__ qual_off, int64_t* __restrict__ src) {
-    const int64_t i = first + (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nseg) return;
-    int64_t q = seg_off[i];
-    const int64_t end = seg_off[i + 1];
-    int64_t records = 0, mapped = 0, taken = 0, err_at = 0;
+// kFill: read w of the table gets its columns, the ends of its three arena
+// ranges (the offsets of read w + 1) and the offsets of its CIGAR, SEQ and
+// QUAL in the inflated stream (src[3 * (w - w_base) ..]) for
+// bases_gather_kernel; a lane writes only reads [out_off[i], + res[i].kept)
+// and only while its arena ranges stay inside the sizes its count pass gave
+// (arena[i]).
+struct BasesSink {
+    struct Args {
+        uint32_t flag_filter;
+        int32_t min_mapq;
+        SegBases* resb;           // count pass: written; fill: the arena sizes of each segment
+        const SegBases* arena;    // fill: words / seq_bytes / qual_bytes are each segment's arena starts
+        int64_t w_base;
+        int32_t *tid, *pos, *l_seq;
+        uint16_t* flag;
+        uint8_t* mapq;
+        int64_t *cig_off, *seq_off, *qual_off, *src;
+    };
+    static constexpr bool kArena = false;
     SegBases c = {0, 0, 0, 0, 0, 0};
-    int32_t err = 0;
-    int64_t w = 0, w_end = 0, cw = 0, sb = 0, qb = 0, cw_end = 0, sb_end = 0, qb_end = 0;
-    if (kFill) {
-        w = out_off[i];
-        w_end = w + res[i].kept;
-        const SegBases a = arena[i];          // words / seq_bytes / qual_bytes: this segment's arena starts
-        cw = a.words;
-        sb = a.seq_bytes;
-        qb = a.qual_bytes;
-        cw_end = cw + resb[i].words;
-        sb_end = sb + resb[i].seq_bytes;
-        qb_end = qb + resb[i].qual_bytes;
+    int64_t cw = 0, sb = 0, qb = 0, cw_end = 0, sb_end = 0, qb_end = 0;
+
+    template <bool kFill>
+    __device__ __forceinline__ void begin(const WalkArgs&, const Args& s, int64_t i) {
+        if (kFill) {
+            const SegBases a = s.arena[i];
+            cw = a.words;
+            sb = a.seq_bytes;
+            qb = a.qual_bytes;
+            cw_end = cw + s.resb[i].words;
+            sb_end = sb + s.resb[i].seq_bytes;
+            qb_end = qb + s.resb[i].qual_bytes;
+        }
     }
+    template <bool kFill>
+    __device__ __forceinline__ Step record(const WalkArgs& a, const Args& s, const uint8_t* r, int32_t bs, int64_t,
+                                           int64_t w, int64_t, bool room) {
+        Step st;
+        mc::gz::RecBases rb;
+        const int rc = mc::gz::rec_bases(r, r + bs, a.n_ref, s.flag_filter, s.min_mapq, rb);
+        if (rc == mc::gz::kRbMalformed) {
+            st.err = kSegMalformed;
+            return st;
+        }
+        st.mapped = rb.mapped;
+        if (rc == mc::gz::kRbDropped) return st;
+        ++c.passed;
+        if (rc == mc::gz::kRbNoSeq) {
+            ++c.no_seq;
+            return st;
+        }
+        if (rc == mc::gz::kRbBadCigar) {
+            ++c.bad_cigar;
+            return st;
+        }
+        const int64_t nb = ((int64_t)rb.l_seq + 1) / 2;
+        const int64_t al = (nb + 3) & ~(int64_t)3;
+        st.kept = true;
+        c.words += rb.n_cigar;
+        c.seq_bytes += al;
+        c.qual_bytes += rb.l_seq;
+        if (kFill && room && cw + rb.n_cigar <= cw_end && sb + al <= sb_end && qb + rb.l_seq <= qb_end) {
+            s.tid[w] = rb.tid;
+            s.pos[w] = rb.pos;
+            s.l_seq[w] = rb.l_seq;
+            s.flag[w] = rb.flag;
+            s.mapq[w] = rb.mapq;
+            int64_t* o = s.src + 3 * (w - s.w_base);
+            o[0] = rb.cig - a.d;
+            o[1] = rb.seq - a.d;
+            o[2] = rb.qual - a.d;
+            cw += rb.n_cigar;
+            sb += al;
+            qb += rb.l_seq;
+            s.cig_off[w + 1] = cw;
+            s.seq_off[w + 1] = sb;
+            s.qual_off[w + 1] = qb;
+            st.wrote = true;
+        }
+        return st;
+    }
+    template <bool kFill>
+    __device__ __forceinline__ void end(const WalkArgs&, const Args& s, int64_t i) {
+        if (!kFill) s.resb[i] = c;
+    }
+};
+
+// The frame: one lane per segment i in [first, nseg).  `landing` (q where the
+// walk stopped) and the three framing checks are what parse_window's rounds
+// rely on, whatever the sink; a fill hands the sink row w only while
+// w < w_end, so it never writes past what its count pass sized.
+template <class Sink, bool kFill>
+__global__ void __launch_bounds__(256)
+walk_kernel(WalkArgs a, typename Sink::Args s) {
+    const int64_t i = a.first + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.nseg) return;
+    int64_t q = a.seg_off[i];
+    const int64_t end = a.seg_off[i + 1];
+    int64_t records = 0, mapped = 0, kept = 0, bytes = 0, err_at = 0;
+    int32_t err = 0;
+    int64_t w = 0, w_end = 0, b = 0;
+    if (kFill) {
+        w = a.out_off[i];
+        w_end = w + a.res[i].kept;
+        if constexpr (Sink::kArena) b = a.byte_off[i];
+    }
+    Sink sink;
+    sink.template begin<kFill>(a, s, i);
     while (q < end) {
-        if (q + 4 > n) {
+        if (q + 4 > a.n) {
             err = kSegIncomplete;
             break;
         }
-        const int32_t bs = mc::gz::ld_i32(d + q);
+        const int32_t bs = mc::gz::ld_i32(a.d + q);
         if (bs < 32) {
             err = kSegBadSize;
             err_at = q;
             break;
         }
-        if (q + 4 + (int64_t)bs > n) {
+        if (q + 4 + (int64_t)bs > a.n) {
             err = kSegIncomplete;
             break;
         }
-        const uint8_t* r = d + q + 4;
-        mc::gz::RecBases rb;
-        const int rc = mc::gz::rec_bases(r, r + bs, n_ref, flag_filter, min_mapq, rb);
-        if (rc == mc::gz::kRbMalformed) {
-            err = kSegMalformed;
+        const Step st = sink.template record<kFill>(a, s, a.d + q + 4, bs, q, w, b, kFill && w < w_end);
+        if (st.err && !st.err_after) {
+            err = st.err;
             err_at = q;
             break;
         }
         q += 4 + (int64_t)bs;
         ++records;
-        mapped += rb.mapped ? 1 : 0;
-        if (rc == mc::gz::kRbDropped) continue;
-        ++c.passed;
-        if (rc == mc::gz::kRbNoSeq) {
-            ++c.no_seq;
-            continue;
+        mapped += st.mapped ? 1 : 0;
+        if (st.err) {
+            err = st.err;
+            err_at = q;
+            break;
         }
-        if (rc == mc::gz::kRbBadCigar) {
-            ++c.bad_cigar;
-            continue;
-        }
-        const int64_t nb = ((int64_t)rb.l_seq + 1) / 2;
-        const int64_t al = (nb + 3) & ~(int64_t)3;
-        ++taken;
-        c.words += rb.n_cigar;
-        c.seq_bytes += al;
-        c.qual_bytes += rb.l_seq;
-        if (kFill && w < w_end && cw + rb.n_cigar <= cw_end && sb + al <= sb_end && qb + rb.l_seq <= qb_end) {
-            tid[w] = rb.tid;
-            pos[w] = rb.pos;
-            l_seq[w] = rb.l_seq;
-            flag[w] = rb.flag;
-            mapq[w] = rb.mapq;
-            int64_t* s = src + 3 * (w - w_base);
-            s[0] = rb.cig - d;
-            s[1] = rb.seq - d;
-            s[2] = rb.qual - d;
-            cw += rb.n_cigar;
-            sb += al;
-            qb += rb.l_seq;
-            cig_off[w + 1] = cw;
-            seq_off[w + 1] = sb;
-            qual_off[w + 1] = qb;
+        kept += st.kept ? 1 : 0;
+        bytes += st.bytes;
+        if (kFill && st.wrote) {
             ++w;
+            b += st.bytes;
         }
     }
+    sink.template end<kFill>(a, s, i);
     if (!kFill) {
-        SegRes s;
-        s.landing = q;
-        s.records = records;
-        s.mapped = mapped;
-        s.kept = taken;
-        s.err_at = err_at;
-        s.bytes = 0;
-        s.err = err;
-        s.pad = 0;
-        res[i] = s;
-        resb[i] = c;
+        SegRes sr;
+        sr.landing = q;
+        sr.records = records;
+        sr.mapped = mapped;
+        sr.kept = kept;
+        sr.err_at = err_at;
+        sr.bytes = bytes;
+        sr.err = err;
+        sr.pad = 0;
+        a.res[i] = sr;
     }
 }
 
@@ -675,13 +668,7 @@ bases_gather_kernel(const uint8_t* __restrict__ d, int64_t n, int64_t w0, int64_
     {
         const uint8_t* s = d + a_seq;
         uint32_t* dst = reinterpret_cast<uint32_t*>(seq + s0);
-        for (int64_t j = gl; j < (s1 - s0) >> 2; j += kGatherLanes) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (4 * j + e < nb) v |= (uint32_t)s[4 * j + e] << (8 * e);
-            dst[j] = v;
-        }
+        for (int64_t j = gl; j < (s1 - s0) >> 2; j += kGatherLanes) dst[j] = ld_dword_within(s, 4 * j, nb);
     }
     {
         const uint8_t* s = d + a_qual;
@@ -754,6 +741,22 @@ double now_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// Events destroyed when the scope ends (entries may still be null).
+struct EventGuard {
+    hipEvent_t* e;
+    size_t n;
+    ~EventGuard() {
+        for (size_t i = 0; i < n; ++i)
+            if (e[i]) (void)hipEventDestroy(e[i]);
+    }
+};
+
+// What a decode keeps of each record: the kept intervals (IntervalsSink),
+// every record as scan's SoA batch (ScanSink), the placed records as
+// experimental()'s read table (ReadsSink), or the base counter's records
+// (BasesSink).
+enum class Mode { Intervals, Scan, Reads, Bases };
+
 }  // namespace
 
 struct mc_bam_gpu {
@@ -765,8 +768,7 @@ struct mc_bam_gpu {
     uint32_t flag_filter = 0;
     DBuf<int32_t> tid, pos, span;     // kept intervals, file order (scan mode: tid, gpos, rlen)
     int64_t n_kept = 0;
-    bool scan_mode = false;           // every record as scan's SoA batch (scan_walk_kernel)
-    bool reads_mode = false;          // the placed records as experimental()'s read table (reads_walk_kernel)
+    Mode mode = Mode::Intervals;      // which sink the walks run with
     int reads_k = 0;
     DBuf<int64_t> rend_pos;           // reads mode: end (pos + reference length)
     DBuf<uint8_t> rbits, rnlen;       // reads mode: bits, name length
@@ -776,8 +778,7 @@ struct mc_bam_gpu {
     DBuf<uint8_t> sseq;               // scan mode: packed nt16 bases
     DBuf<int64_t> boff;               // scan mode: per-segment byte offsets of the fill
     int64_t n_bytes = 0;
-    // bases mode (bases_walk_kernel + bases_gather_kernel): tid, pos and span (= l_seq) above, then
-    bool bases_mode = false;
+    // bases mode (BasesSink + bases_gather_kernel): tid, pos and span (= l_seq) above, then
     int32_t min_mapq = 0;
     DBuf<int64_t> bcig_off, bseq_off, bqual_off;   // [n_kept + 1] each, absolute into the arenas
     DBuf<uint32_t> bcigar;                          // CIGAR words
@@ -906,14 +907,8 @@ int upload_file_range(mc_bam_gpu* g, int fd, size_t off, size_t len, uint8_t* ds
     // (pinning 64 MiB takes a few ms; a new handle allocates them all)
     HIP_TRY(g->stage[0].reserve(kSlice));
     hipEvent_t done[kStage] = {};
+    EventGuard guard{done, kStage};
     for (auto& e : done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    struct Guard {
-        hipEvent_t* e;
-        ~Guard() {
-            for (int i = 0; i < kStage; ++i)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } guard{done};
     const int64_t ns = (int64_t)((len + kSlice - 1) / kSlice);
     // (8 / 24 / 32 readers instead of 16: within noise, profiles/r04/r04n_e2e.json)
     const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)g->nt, std::min(len, kSlice) >> 20));
@@ -1037,6 +1032,72 @@ int sync_segments(mc_bam_gpu* g, int64_t o, int64_t n, int64_t i0, int64_t nseg,
     return MC_OK;
 }
 
+// One lane per segment of [a.first, a.nseg), 256 to a workgroup.
+template <class Sink>
+int launch_sink(bool fill, hipStream_t st, const WalkArgs& a, const typename Sink::Args& s) {
+    const int grid = (int)((a.nseg - a.first + 255) / 256);
+    if (fill) walk_kernel<Sink, true><<<grid, 256, 0, st>>>(a, s);
+    else walk_kernel<Sink, false><<<grid, 256, 0, st>>>(a, s);
+    HIP_TRY(hipGetLastError());
+    return MC_OK;
+}
+
+// The walk of segments [first, nseg) of inflated[.., n) with the mode's sink:
+// the count pass into g->res (and g->resb), or the fill of the rows behind
+// g->out_off (base: the stream offset of inflated[0], for the per-contig
+// table).  A count pass gets the sink's scalars and no columns.
+int launch_walk(mc_bam_gpu* g, bool fill, int64_t first, int64_t nseg, int64_t n, int64_t base = 0) {
+    const WalkArgs a = {g->inflated.p, n, g->seg_off.p, first, nseg, (int32_t)g->hdr.names.size(), g->res.p,
+                        fill ? g->out_off.p : nullptr, fill ? g->boff.p : nullptr};
+    switch (g->mode) {
+        case Mode::Intervals: {
+            IntervalsSink::Args s = {};
+            s.flag_filter = g->flag_filter;
+            s.tid_map = g->tid_map.p;
+            if (fill) {
+                s.tid = g->tid.p, s.pos = g->pos.p, s.span = g->span.p;
+                s.ext = g->ext.p;
+                s.base = base;
+            }
+            return launch_sink<IntervalsSink>(fill, g->stream, a, s);
+        }
+        case Mode::Scan: {
+            ScanSink::Args s = {};
+            if (fill) {   // (rlen and gpos live in the span and pos columns)
+                s.rlen = g->span.p, s.flag = g->sflag.p, s.gpos = g->pos.p, s.gisize = g->sgisize.p, s.tid = g->tid.p;
+                s.seq_off = g->soff.p, s.seq = g->sseq.p;
+            }
+            return launch_sink<ScanSink>(fill, g->stream, a, s);
+        }
+        case Mode::Reads: {
+            ReadsSink::Args s = {};
+            s.k = g->reads_k;
+            s.tid_map = g->subset ? g->tid_map.p : nullptr;
+            if (fill) {
+                s.tid = g->tid.p, s.pos = g->pos.p, s.end_pos = g->rend_pos.p, s.flag = g->sflag.p;
+                s.bits = g->rbits.p, s.kmer = g->rkmer.p, s.name_len = g->rnlen.p;
+                s.name_off = g->soff.p, s.names = g->sseq.p;
+            }
+            return launch_sink<ReadsSink>(fill, g->stream, a, s);
+        }
+        case Mode::Bases: {
+            BasesSink::Args s = {};
+            s.flag_filter = g->flag_filter;
+            s.min_mapq = g->min_mapq;
+            s.resb = g->resb.p;
+            if (fill) {
+                s.arena = g->barena.p;
+                s.w_base = g->n_kept;
+                s.tid = g->tid.p, s.pos = g->pos.p, s.l_seq = g->span.p, s.flag = g->bflag.p, s.mapq = g->bmapq.p;
+                s.cig_off = g->bcig_off.p, s.seq_off = g->bseq_off.p, s.qual_off = g->bqual_off.p;
+                s.src = g->bsrc.p;
+            }
+            return launch_sink<BasesSink>(fill, g->stream, a, s);
+        }
+    }
+    return MC_OK;
+}
+
 // Bases mode's fill of one parsed window: g->res / g->out_off hold the final
 // counts and read offsets of its nseg segments, g->hresb the host copy of the
 // second per-segment array; `total` reads join the table.  The arenas grow
@@ -1090,13 +1151,7 @@ int fill_bases(mc_bam_gpu* g, int64_t n, int64_t nseg, int64_t total) {
         HIP_TRY(hipMemcpyAsync(g->barena.p, start.data(), nseg * sizeof(SegBases), hipMemcpyHostToDevice, st));
         // (a read the fill skipped keeps these negative source offsets, and the gather refuses it)
         HIP_TRY(hipMemsetAsync(g->bsrc.p, 0xFF, 3 * (size_t)total * 8, st));
-        const int grid = (int)((nseg + 255) / 256);
-        bases_walk_kernel<true><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, 0, nseg, (int32_t)g->hdr.names.size(),
-                                                      g->flag_filter, g->min_mapq, g->res.p, g->resb.p, g->out_off.p,
-                                                      g->barena.p, g->n_kept, g->tid.p, g->pos.p, g->span.p,
-                                                      g->bflag.p, g->bmapq.p, g->bcig_off.p, g->bseq_off.p,
-                                                      g->bqual_off.p, g->bsrc.p);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_walk(g, true, 0, nseg, n)) return rc;
         constexpr int per_block = 256 / kGatherLanes;
         const int64_t blocks = (total + per_block - 1) / per_block;
         MC_REQUIRE(blocks < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^35 reads in one window");
@@ -1123,8 +1178,6 @@ int fill_bases(mc_bam_gpu* g, int64_t n, int64_t nseg, int64_t total) {
 // offset of inflated[0] (the per-contig table's offsets).
 int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* consumed, int64_t base = 0) {
     hipStream_t st = g->stream;
-    const int32_t n_ref = (int32_t)g->hdr.names.size();
-    const uint8_t* d = g->inflated.p;
     const int64_t nseg = std::max<int64_t>(1, (n - o + kSeg - 1) / kSeg);
     HIP_TRY(g->seg_off.reserve(nseg + 1));
     HIP_TRY(g->found.reserve(nseg + 1));
@@ -1132,7 +1185,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     HIP_TRY(g->res.reserve(nseg));
     HIP_TRY(g->h64.reserve(2 * (nseg + 1)));   // (scan mode: the byte offsets after the record offsets)
     HIP_TRY(g->hres.reserve(nseg));
-    if (g->bases_mode) {
+    if (g->mode == Mode::Bases) {
         HIP_TRY(g->resb.reserve(nseg));
         HIP_TRY(g->barena.reserve(nseg));
         HIP_TRY(g->hresb.reserve(nseg));
@@ -1159,26 +1212,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
                    round);
         std::memcpy(h, seg.data() + first, (nseg + 1 - first) * 8);
         HIP_TRY(hipMemcpyAsync(g->seg_off.p + first, h, (nseg + 1 - first) * 8, hipMemcpyHostToDevice, st));
-        const int grid = (int)((nseg - first + 255) / 256);
-        if (g->bases_mode)
-            bases_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->flag_filter,
-                                                           g->min_mapq, g->res.p, g->resb.p, nullptr, nullptr, 0,
-                                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                           nullptr, nullptr, nullptr);
-        else if (g->scan_mode)
-            scan_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->res.p, nullptr,
-                                                          nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                          nullptr, nullptr);
-        else if (g->reads_mode)
-            reads_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->reads_k,
-                                                           g->res.p, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                           g->subset ? g->tid_map.p : nullptr);
-        else
-            rec_walk_kernel<false><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, first, nseg, n_ref, g->flag_filter,
-                                                         g->res.p, nullptr, nullptr, nullptr, nullptr,
-                                                         g->tid_map.p, nullptr, 0);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch_walk(g, false, first, nseg, n)) return rc;
         HIP_TRY(hipMemcpyAsync(R + first, g->res.p + first, (nseg - first) * sizeof(SegRes),
                                hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -1240,7 +1274,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     // bases mode: every segment's last count pass (the rounds re-walk only segments they moved)
     SegBases* B = g->hresb.p;
     const SegBases kNoBases = {0, 0, 0, 0, 0, 0};
-    if (g->bases_mode) {
+    if (g->mode == Mode::Bases) {
         HIP_TRY(hipMemcpyAsync(B, g->resb.p, nseg * sizeof(SegBases), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -1251,7 +1285,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
         SegRes& r = R[i];
         if (seg[i] >= seg[i + 1] && seg[i] == n) {   // empty tail segment
             r.kept = r.records = r.mapped = r.bytes = 0;
-            if (g->bases_mode) B[i] = kNoBases;
+            if (g->mode == Mode::Bases) B[i] = kNoBases;
         }
         koff[i] = g->n_kept + total;
         bo[i] = g->n_bytes + bytes;
@@ -1265,7 +1299,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
                 koff[j] = g->n_kept + total;
                 bo[j] = g->n_bytes + bytes;
                 R[j].kept = R[j].records = R[j].mapped = R[j].bytes = 0;
-                if (g->bases_mode) B[j] = kNoBases;
+                if (g->mode == Mode::Bases) B[j] = kNoBases;
             }
             break;
         }
@@ -1276,7 +1310,7 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     std::memcpy(h, koff.data(), nseg * 8);
     HIP_TRY(hipMemcpyAsync(g->out_off.p, h, nseg * 8, hipMemcpyHostToDevice, st));
     const size_t need = (size_t)(g->n_kept + total) + 4;
-    if (g->bases_mode) {
+    if (g->mode == Mode::Bases) {
         if (int rc = fill_bases(g, n, nseg, total)) return rc;
         g->hdr.n_records += records;
         g->hdr.n_mapped += mapped;
@@ -1286,44 +1320,26 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     HIP_TRY(g->tid.reserve(need, st, g->n_kept));
     HIP_TRY(g->pos.reserve(need, st, g->n_kept));
     HIP_TRY(g->span.reserve(need, st, g->n_kept));
-    if (g->scan_mode || g->reads_mode) {
+    if (g->mode != Mode::Intervals) {   // the columns and the byte arena scan and reads mode share
         HIP_TRY(g->sflag.reserve(need, st, g->n_kept));
         HIP_TRY(g->soff.reserve(need + 1, st, g->n_kept + 1));
         HIP_TRY(g->sseq.reserve((size_t)(g->n_bytes + bytes) + 16, st, (size_t)g->n_bytes));
         HIP_TRY(g->boff.reserve(nseg + 1));
         std::memcpy(h + nseg + 1, bo.data(), nseg * 8);
         HIP_TRY(hipMemcpyAsync(g->boff.p, h + nseg + 1, nseg * 8, hipMemcpyHostToDevice, st));
-        const int grid = (int)((nseg + 255) / 256);
-        if (g->scan_mode) {
-            HIP_TRY(g->sgisize.reserve(need, st, g->n_kept));
-            if (g->n_kept == 0) HIP_TRY(hipMemsetAsync(g->soff.p, 0, 8, st));
-            if (total) {
-                scan_walk_kernel<true><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, 0, nseg, n_ref, g->res.p,
-                                                             g->out_off.p, g->boff.p, g->span.p, g->sflag.p, g->pos.p,
-                                                             g->sgisize.p, g->tid.p, g->soff.p, g->sseq.p);
-                HIP_TRY(hipGetLastError());
-            }
-        } else {
-            HIP_TRY(g->rend_pos.reserve(need, st, g->n_kept));
-            HIP_TRY(g->rbits.reserve(need, st, g->n_kept));
-            HIP_TRY(g->rkmer.reserve(need, st, g->n_kept));
-            HIP_TRY(g->rnlen.reserve(need, st, g->n_kept));
-            if (total) {
-                reads_walk_kernel<true><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, 0, nseg, n_ref, g->reads_k,
-                                                              g->res.p, g->out_off.p, g->boff.p, g->tid.p, g->pos.p,
-                                                              g->rend_pos.p, g->sflag.p, g->rbits.p, g->rkmer.p,
-                                                              g->rnlen.p, g->soff.p, g->sseq.p,
-                                                              g->subset ? g->tid_map.p : nullptr);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-    } else if (total || g->ext.p) {
-        const int grid = (int)((nseg + 255) / 256);
-        rec_walk_kernel<true><<<grid, 256, 0, st>>>(d, n, g->seg_off.p, 0, nseg, n_ref, g->flag_filter, g->res.p,
-                                                    g->out_off.p, g->tid.p, g->pos.p, g->span.p, g->tid_map.p,
-                                                    g->ext.p, base);
-        HIP_TRY(hipGetLastError());
     }
+    if (g->mode == Mode::Scan) {
+        HIP_TRY(g->sgisize.reserve(need, st, g->n_kept));
+        if (g->n_kept == 0) HIP_TRY(hipMemsetAsync(g->soff.p, 0, 8, st));
+    } else if (g->mode == Mode::Reads) {
+        HIP_TRY(g->rend_pos.reserve(need, st, g->n_kept));
+        HIP_TRY(g->rbits.reserve(need, st, g->n_kept));
+        HIP_TRY(g->rkmer.reserve(need, st, g->n_kept));
+        HIP_TRY(g->rnlen.reserve(need, st, g->n_kept));
+    }
+    // (intervals mode's fill also builds the per-contig table, kept records or not)
+    if (total || (g->mode == Mode::Intervals && g->ext.p))
+        if (int rc = launch_walk(g, true, 0, nseg, n, base)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     g->n_kept += total;
     g->n_bytes += bytes;
@@ -1333,21 +1349,10 @@ int parse_window(mc_bam_gpu* g, int64_t o, int64_t n, bool partial, int64_t* con
     return MC_OK;
 }
 
-// BGZF header at o of d[0, n): its total size (0 if none)
-size_t bgzf_hdr(const uint8_t* d, size_t n, size_t o) {
-    if (o + 18 > n || d[o] != 31 || d[o + 1] != 139 || d[o + 2] != 8 || !(d[o + 3] & 4)) return 0;
-    const uint16_t xlen = rd16(d + o + 10);
-    size_t bsize = 0;
-    for (size_t x = o + 12; x + 4 <= o + 12 + xlen && x + 4 <= n;) {
-        const uint16_t slen = rd16(d + x + 2);
-        if (d[x] == 66 && d[x + 1] == 67 && slen == 2 && x + 6 <= n) bsize = (size_t)rd16(d + x + 4) + 1;
-        x += 4 + slen;
-    }
-    return bsize >= (size_t)xlen + 20 && o + bsize <= n ? bsize : 0;
-}
-
 // BGZF header of the block at file offset o, its first bytes in h[0, hn):
-// the block's total size, 0 if none (bgzf_hdr's rules; n = the file size).
+// the block's total size, 0 if none (n = the file size): the gzip magic with
+// an extra field, a BC subfield of length 2 inside the bytes given, and a
+// block that holds its header and trailer and ends inside the file.
 size_t bgzf_hdr_at(const uint8_t* h, size_t hn, size_t o, size_t n) {
     if (hn < 18 || o + 18 > n || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return 0;
     const size_t xlen = rd16(h + 10);
@@ -1358,6 +1363,11 @@ size_t bgzf_hdr_at(const uint8_t* h, size_t hn, size_t o, size_t n) {
         x += 4 + slen;
     }
     return bsize >= xlen + 20 && o + bsize <= n ? bsize : 0;
+}
+
+// BGZF header at o of d[0, n): its total size (0 if none)
+size_t bgzf_hdr(const uint8_t* d, size_t n, size_t o) {
+    return o + 18 > n ? 0 : bgzf_hdr_at(d + o, n - o, o, n);
 }
 
 bool pread_all(int fd, uint8_t* buf, size_t len, size_t off) {
@@ -1599,6 +1609,49 @@ struct BgUpload {
     }
 };
 
+// Starts the background upload of virtual bytes [0, vsize) (vm: the map,
+// nullptr: the file itself) into g->comp[0], which the caller has reserved.
+void start_bg_upload(mc_bam_gpu* g, BgUpload& bg, int fd, size_t vsize, const VMap* vm) {
+    bg.t = std::thread([g, &bg, fd, vsize, vm]() {
+        if (hipSetDevice(g->device) != hipSuccess) {
+            bg.rc = MC_E_HIP;
+            bg.msg = "hipSetDevice failed in the upload thread";
+        } else {
+            bg.rc = upload_file_range(g, fd, 0, vsize, g->comp[0].p, g->up_stream, &bg.progress, &bg.cancel, vm);
+            if (bg.rc) bg.msg = mc::last_error();
+        }
+        bg.finished.store(true, std::memory_order_release);
+    });
+}
+
+// Runs of blocks [b0, b1) of at most `limit` inflated bytes each (at least
+// one block): the resident decode's pieces, the windowed decode's windows.
+std::vector<std::pair<size_t, size_t>> cut_blocks(const std::vector<Block>& blocks, size_t limit) {
+    std::vector<std::pair<size_t, size_t>> cuts;
+    for (size_t b0 = 0; b0 < blocks.size();) {
+        size_t b1 = b0, sz = 0;
+        while (b1 < blocks.size() && (b1 == b0 || sz + blocks[b1].isize <= limit)) sz += blocks[b1++].isize;
+        cuts.emplace_back(b0, b1);
+        b0 = b1;
+    }
+    return cuts;
+}
+
+// The inflate kernel flagged a failure among the nb blocks from blocks[b0]
+// (their status words at g->status): reports the first one (vm: the map its
+// offsets are virtual in, nullptr: file offsets).
+int report_inflate_error(mc_bam_gpu* g, const VMap* vm, const std::vector<Block>& blocks, size_t b0, int64_t nb) {
+    std::vector<int> sv(nb);
+    HIP_TRY(hipMemcpy(sv.data(), g->status.p, nb * sizeof(int), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < nb; ++i)
+        if (sv[i]) {
+            mc::set_error("BGZF inflate failed in %s (block at file offset %zu: %s)", g->path.c_str(),
+                          file_off(vm, blocks[b0 + i].off), gz_err_msg(sv[i]));
+            return MC_E_IO;
+        }
+    return MC_OK;
+}
+
 // Inflate lanes the grid is sized for: kGzLanes per wave, as many waves per
 // CU as the kernel's LDS and registers allow on this device (at most
 // kGzWavesPerCu, the count for gfx950's 160 KiB of LDS per CU).
@@ -1630,13 +1683,7 @@ int inflate_resident(mc_bam_gpu* g, int fd, const VMap* vm, size_t vsize, const 
     const int64_t nb = (int64_t)blocks.size();
     hipStream_t st = g->stream;
     const size_t piece = std::min<size_t>(4ull << 30, std::max<size_t>(256ull << 20, total / MC_GZ_PIECES));
-    std::vector<std::pair<size_t, size_t>> pcs;
-    for (size_t b0 = 0; b0 < blocks.size();) {
-        size_t b1 = b0, sz = 0;
-        while (b1 < blocks.size() && (b1 == b0 || sz + blocks[b1].isize <= piece)) sz += blocks[b1++].isize;
-        pcs.emplace_back(b0, b1);
-        b0 = b1;
-    }
+    const std::vector<std::pair<size_t, size_t>> pcs = cut_blocks(blocks, piece);
     HIP_TRY(g->comp[0].reserve(vsize + kPad));
     HIP_TRY(g->hblk.reserve(nb));
     for (int64_t i = 0; i < nb; ++i) {
@@ -1657,25 +1704,13 @@ int inflate_resident(mc_bam_gpu* g, int fd, const VMap* vm, size_t vsize, const 
         ks[k] = g->kstream[k - 1];
     }
     hipEvent_t ev[2] = {nullptr, nullptr};
+    EventGuard evg{ev, 2};
     for (auto& e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 2; ++i)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
     HIP_TRY(hipEventRecord(ev[0], st));   // block table, status flag and pad are set
     for (int k = 1; k < kGzPieceStreams; ++k) HIP_TRY(hipStreamWaitEvent(ks[k], ev[0], 0));
     // each launch between two timing events (t_kernel: their durations summed)
     std::vector<hipEvent_t> kev(2 * pcs.size(), nullptr);
-    struct KevGuard {
-        std::vector<hipEvent_t>& e;
-        ~KevGuard() {
-            for (auto x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-    } kevg{kev};
+    EventGuard kevg{kev.data(), kev.size()};
     for (auto& e : kev) HIP_TRY(hipEventCreate(&e));
     double t_first = now_s();
     for (size_t p = 0; p < pcs.size(); ++p) {
@@ -1727,22 +1762,12 @@ int inflate_resident(mc_bam_gpu* g, int fd, const VMap* vm, size_t vsize, const 
         HIP_TRY(hipEventElapsedTime(&ms, kev[2 * p], kev[2 * p + 1]));
         g->t_kernel += ms;
     }
-    if (any) {
-        std::vector<int> sv(nb);
-        HIP_TRY(hipMemcpy(sv.data(), g->status.p, nb * sizeof(int), hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < nb; ++i)
-            if (sv[i]) {
-                mc::set_error("BGZF inflate failed in %s (block at file offset %zu: %s)", g->path.c_str(),
-                              file_off(vm, blocks[i].off), gz_err_msg(sv[i]));
-                return MC_E_IO;
-            }
-    }
-    return MC_OK;
+    return any ? report_inflate_error(g, vm, blocks, 0, nb) : MC_OK;
 }
 
 // The per-contig table of the record walk, zeroed (n_ref + 1 entries).
 int init_ext(mc_bam_gpu* g) {
-    if (g->scan_mode || g->reads_mode || g->bases_mode) return MC_OK;   // (no extents table)
+    if (g->mode != Mode::Intervals) return MC_OK;   // (no extents table)
     const size_t m = g->hdr.names.size() + 1;
     HIP_TRY(g->ext.reserve(m));
     HIP_TRY(hipMemsetAsync(g->ext.p, 0, m * sizeof(ExtAcc), g->stream));
@@ -1785,17 +1810,7 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
         HIP_TRY(hipMemGetInfo(&free_b, &tot_b));
         if (mf.size * 4 <= free_b / 2) {
             HIP_TRY(g->comp[0].reserve(mf.size + kPad));
-            bg.t = std::thread([&]() {
-                if (hipSetDevice(g->device) != hipSuccess) {
-                    bg.rc = MC_E_HIP;
-                    bg.msg = "hipSetDevice failed in the upload thread";
-                } else {
-                    bg.rc = upload_file_range(g, mf.fd, 0, mf.size, g->comp[0].p, g->up_stream, &bg.progress,
-                                              &bg.cancel);
-                    if (bg.rc) bg.msg = mc::last_error();
-                }
-                bg.finished.store(true, std::memory_order_release);
-            });
+            start_bg_upload(g, bg, mf.fd, mf.size, nullptr);
         }
     }
     if (int rc = scan_blocks_pread(mf.fd, mf.size, g->nt, g->path.c_str(), blocks, total)) return rc;
@@ -1805,14 +1820,9 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
     g->compressed_bytes = (int64_t)mf.size;
     const size_t win = (size_t)std::max<int64_t>(window_bytes > 0 ? window_bytes : (4ll << 30), 1 << 20);
     hipStream_t st = g->stream;
-    hipEvent_t ev[4];
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around a window's inflate launch
+    EventGuard evg{ev, 2};
     for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
     const int64_t max_lanes = gz_max_lanes(g->device);
     if (window_bytes <= 0 && !blocks.empty()) {
         // resident when the compressed file, its inflated stream and the
@@ -1823,7 +1833,7 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
         HIP_TRY(hipMemGetInfo(&free_b, &tot_b));
         if (bg.t.joinable()) free_b += g->comp[0].cap;
         // (bases mode copies nearly every inflated byte into its arenas: as much again)
-        if (resident_fits(mf.size, total, blocks.size(), max_lanes, free_b, g->bases_mode ? total : 0)) {
+        if (resident_fits(mf.size, total, blocks.size(), max_lanes, free_b, g->mode == Mode::Bases ? total : 0)) {
             const int rc = gpu_decode_resident(g, mf, blocks, total, max_lanes, bg.t.joinable() ? &bg : nullptr);
             if (rc == MC_OK && bg.t.joinable()) {
                 if (int urc = bg.join()) return urc;
@@ -1839,13 +1849,7 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
         g->comp[0].release();   // (the windows size their own buffers)
     }
     // windows of blocks (<= win inflated bytes each, at least one block)
-    std::vector<std::pair<size_t, size_t>> wins;
-    for (size_t b0 = 0; b0 < blocks.size();) {
-        size_t b1 = b0, wsize = 0;
-        while (b1 < blocks.size() && (b1 == b0 || wsize + blocks[b1].isize <= win)) wsize += blocks[b1++].isize;
-        wins.emplace_back(b0, b1);
-        b0 = b1;
-    }
+    const std::vector<std::pair<size_t, size_t>> wins = cut_blocks(blocks, win);
     MC_REQUIRE(!wins.empty(), MC_E_IO, "%s: no valid BAM header", g->path.c_str());
     auto crange = [&](size_t w, size_t* coff, size_t* clen) {
         *coff = blocks[wins[w].first].off;
@@ -1934,7 +1938,6 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
         }
         HIP_TRY(g->status.reserve(nb + 1));
         HIP_TRY(hipMemsetAsync(g->status.p + nb, 0, sizeof(int), st));
-        // a multiple of the workgroup: every launched lane owns a scratch slot
         // a multiple of the lanes per workgroup: every launched lane owns a scratch slot
         const int64_t lanes = std::min<int64_t>(max_lanes, (nb + kGzLanes - 1) / kGzLanes * kGzLanes);
         HIP_TRY(g->scratch.reserve((size_t)lanes * kGzSlotWords));
@@ -1950,38 +1953,13 @@ int gpu_decode(mc_bam_gpu* g, int64_t window_bytes) {
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
         g->t_inflate += ms;
         g->t_kernel += ms;
-        if (any) {
-            std::vector<int> s(nb);
-            HIP_TRY(hipMemcpy(s.data(), g->status.p, nb * sizeof(int), hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < nb; ++i)
-                if (s[i]) {
-                    mc::set_error("BGZF inflate failed in %s (block at file offset %zu: %s)", g->path.c_str(),
-                                  blocks[b0 + i].off, gz_err_msg(s[i]));
-                    return MC_E_IO;
-                }
-        }
+        if (any)
+            if (int rc = report_inflate_error(g, nullptr, blocks, b0, nb)) return rc;
         if (!have_header) {
-            // header from a growing prefix of the inflated bytes
-            size_t p = std::min<size_t>(n, 1 << 20);
-            std::vector<uint8_t> hb;
-            for (;;) {
-                hb.resize(p);
-                HIP_TRY(hipMemcpy(hb.data(), g->inflated.p, p, hipMemcpyDeviceToHost));
-                std::vector<std::string> names;
-                std::vector<int64_t> lens;
-                size_t ho = 0;
-                if (parse_header(hb.data(), p, g->path.c_str(), names, lens, &ho) == MC_OK) {
-                    g->hdr.names = std::move(names);
-                    g->hdr.lens = std::move(lens);
-                    o = (int64_t)ho;
-                    have_header = true;
-                    if (int rc = init_ext(g)) return rc;
-                    break;
-                }
-                if (p >= n) break;
-                p = std::min(n, p * 4);
-            }
-            if (!have_header) {
+            if (int rc = header_from_prefix(g, n, &o, &have_header)) return rc;
+            if (have_header) {
+                if (int rc = init_ext(g)) return rc;
+            } else {
                 // the header continues in the next window: keep everything
                 MC_REQUIRE(!last, MC_E_IO, "%s: no valid BAM header", g->path.c_str());
                 carry = n;
@@ -2135,17 +2113,7 @@ int gpu_decode_extents(mc_bam_gpu* g, int32_t n_ref_in, const mc_contig_extent* 
         HIP_TRY(hipMemGetInfo(&free_b, &tot_b));
         if (vsize * 4 <= free_b / 2) {
             HIP_TRY(g->comp[0].reserve(vsize + kPad));
-            bg.t = std::thread([&]() {
-                if (hipSetDevice(g->device) != hipSuccess) {
-                    bg.rc = MC_E_HIP;
-                    bg.msg = "hipSetDevice failed in the upload thread";
-                } else {
-                    bg.rc = upload_file_range(g, mf.fd, 0, vsize, g->comp[0].p, g->up_stream, &bg.progress,
-                                              &bg.cancel, &vm);
-                    if (bg.rc) bg.msg = mc::last_error();
-                }
-                bg.finished.store(true, std::memory_order_release);
-            });
+            start_bg_upload(g, bg, mf.fd, vsize, &vm);
         }
     }
     std::vector<Block> blocks;
@@ -2251,19 +2219,30 @@ uint64_t voff_of(const std::vector<Block>& b, const std::vector<size_t>& nz, siz
     return k + 1 < b.size() ? (uint64_t)b[k + 1].off << 16 : (uint64_t)file_size << 16;
 }
 
-int open_common(const char* path, int device, int n_threads, uint32_t flag_filter,
-                std::unique_ptr<mc_bam_gpu>& g) {
+// The body of the mc_bam_gpu_open* entry points behind their argument checks:
+// a handle on `device`, `configure` sets its mode, `decode` fills it.
+template <class Configure, class Decode>
+int open_with(const char* path, int device, int n_threads, uint32_t flag_filter, mc_bam_gpu** out,
+              Configure configure, Decode decode) {
+    *out = nullptr;
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     MC_REQUIRE(device >= 0 && device < ndev, MC_E_INVALID, "no HIP device %d", device);
     HIP_TRY(hipSetDevice(device));
-    g.reset(new mc_bam_gpu());
+    std::unique_ptr<mc_bam_gpu> g(new mc_bam_gpu());
     g->path = path;
     g->device = device;
     g->nt = n_threads > 0 ? n_threads : std::min(16, n_threads_or_all(0));   // file reads only
     g->flag_filter = flag_filter;
     HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&g->up_stream, hipStreamNonBlocking));
+    configure(g.get());
+    const double t0 = now_s();
+    if (int rc = decode(g.get())) return rc;
+    g->t_open = (now_s() - t0) * 1e3;   // total_ms + the mapping's teardown
+    // (the staging and parse buffers go with the handle: a hipFree of the
+    // multi-GB windows here sat on the open's critical path)
+    *out = g.release();
     return MC_OK;
 }
 
@@ -2272,30 +2251,15 @@ int open_common(const char* path, int device, int n_threads, uint32_t flag_filte
 extern "C" int mc_bam_gpu_open(const char* path, int device, int n_threads, uint32_t flag_filter,
                                int64_t window_bytes, mc_bam_gpu** out) {
     MC_REQUIRE(path && out, MC_E_INVALID, "null argument");
-    *out = nullptr;
-    std::unique_ptr<mc_bam_gpu> g;
-    if (int rc = open_common(path, device, n_threads, flag_filter, g)) return rc;
-    const double t0 = now_s();
-    if (int rc = gpu_decode(g.get(), window_bytes)) return rc;
-    g->t_open = (now_s() - t0) * 1e3;   // total_ms + the mapping's teardown
-    // (the staging and parse buffers go with the handle: a hipFree of the
-    // multi-GB windows here sat on the open's critical path)
-    *out = g.release();
-    return MC_OK;
+    return open_with(path, device, n_threads, flag_filter, out, [](mc_bam_gpu*) {},
+                     [&](mc_bam_gpu* g) { return gpu_decode(g, window_bytes); });
 }
 
 extern "C" int mc_bam_gpu_open_scan(const char* path, int device, int n_threads, int64_t window_bytes,
                                     mc_bam_gpu** out) {
     MC_REQUIRE(path && out, MC_E_INVALID, "null argument");
-    *out = nullptr;
-    std::unique_ptr<mc_bam_gpu> g;
-    if (int rc = open_common(path, device, n_threads, 0, g)) return rc;
-    g->scan_mode = true;
-    const double t0 = now_s();
-    if (int rc = gpu_decode(g.get(), window_bytes)) return rc;
-    g->t_open = (now_s() - t0) * 1e3;
-    *out = g.release();
-    return MC_OK;
+    return open_with(path, device, n_threads, 0, out, [](mc_bam_gpu* g) { g->mode = Mode::Scan; },
+                     [&](mc_bam_gpu* g) { return gpu_decode(g, window_bytes); });
 }
 
 extern "C" int mc_bam_gpu_scan_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_rlen,
@@ -2304,7 +2268,7 @@ extern "C" int mc_bam_gpu_scan_device(const mc_bam_gpu* g, int64_t* n, const int
                                       int64_t* seq_bytes) {
     MC_REQUIRE(g && n && d_rlen && d_flag && d_gpos && d_gisize && d_tid && d_seq_off && d_seq && seq_bytes,
                MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->scan_mode, MC_E_STATE, "not a scan-mode decode (mc_bam_gpu_open_scan)");
+    MC_REQUIRE(g->mode == Mode::Scan, MC_E_STATE, "not a scan-mode decode (mc_bam_gpu_open_scan)");
     *n = g->n_kept;
     *d_rlen = g->span.p;
     *d_flag = g->sflag.p;
@@ -2321,16 +2285,8 @@ extern "C" int mc_bam_gpu_open_reads(const char* path, int device, int n_threads
                                      mc_bam_gpu** out) {
     MC_REQUIRE(path && out, MC_E_INVALID, "null argument");
     MC_REQUIRE(k >= 1 && k <= 16, MC_E_INVALID, "k-mer length %d outside [1, 16]", k);
-    *out = nullptr;
-    std::unique_ptr<mc_bam_gpu> g;
-    if (int rc = open_common(path, device, n_threads, 0, g)) return rc;
-    g->reads_mode = true;
-    g->reads_k = k;
-    const double t0 = now_s();
-    if (int rc = gpu_decode(g.get(), window_bytes)) return rc;
-    g->t_open = (now_s() - t0) * 1e3;
-    *out = g.release();
-    return MC_OK;
+    return open_with(path, device, n_threads, 0, out, [&](mc_bam_gpu* g) { g->mode = Mode::Reads, g->reads_k = k; },
+                     [&](mc_bam_gpu* g) { return gpu_decode(g, window_bytes); });
 }
 
 extern "C" int mc_bam_gpu_open_reads_extents(const char* path, int device, int n_threads, int k, int32_t n_ref,
@@ -2340,16 +2296,8 @@ extern "C" int mc_bam_gpu_open_reads_extents(const char* path, int device, int n
                    n_no_coor >= 0,
                MC_E_INVALID, "bad argument");
     MC_REQUIRE(k >= 1 && k <= 16, MC_E_INVALID, "k-mer length %d outside [1, 16]", k);
-    *out = nullptr;
-    std::unique_ptr<mc_bam_gpu> g;
-    if (int rc = open_common(path, device, n_threads, 0, g)) return rc;
-    g->reads_mode = true;
-    g->reads_k = k;
-    const double t0 = now_s();
-    if (int rc = gpu_decode_extents(g.get(), n_ref, ext, n_no_coor, n_sel, sel)) return rc;
-    g->t_open = (now_s() - t0) * 1e3;
-    *out = g.release();
-    return MC_OK;
+    return open_with(path, device, n_threads, 0, out, [&](mc_bam_gpu* g) { g->mode = Mode::Reads, g->reads_k = k; },
+                     [&](mc_bam_gpu* g) { return gpu_decode_extents(g, n_ref, ext, n_no_coor, n_sel, sel); });
 }
 
 extern "C" int mc_bam_gpu_reads_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_tid,
@@ -2359,7 +2307,7 @@ extern "C" int mc_bam_gpu_reads_device(const mc_bam_gpu* g, int64_t* n, const in
     MC_REQUIRE(g && n && d_tid && d_pos && d_end && d_flag && d_bits && d_kmer && d_name_len && d_name_off &&
                    d_names && name_bytes,
                MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->reads_mode, MC_E_STATE, "not a reads-mode decode (mc_bam_gpu_open_reads)");
+    MC_REQUIRE(g->mode == Mode::Reads, MC_E_STATE, "not a reads-mode decode (mc_bam_gpu_open_reads)");
     *n = g->n_kept;
     *d_tid = g->tid.p;
     *d_pos = g->pos.p;
@@ -2380,7 +2328,7 @@ extern "C" int mc_bam_gpu_reads_copy(const mc_bam_gpu* g, int32_t* tid, int32_t*
     MC_REQUIRE(g && ((tid && pos && end && flag && bits && kmer && name_len && name_off) || !g->n_kept) &&
                    (names || !g->n_bytes),
                MC_E_INVALID, "null argument");   // (an empty table: no buffers needed)
-    MC_REQUIRE(g->reads_mode, MC_E_STATE, "not a reads-mode decode (mc_bam_gpu_open_reads)");
+    MC_REQUIRE(g->mode == Mode::Reads, MC_E_STATE, "not a reads-mode decode (mc_bam_gpu_open_reads)");
     HIP_TRY(hipSetDevice(g->device));
     const size_t n = (size_t)g->n_kept;
     hipStream_t st = g->stream;
@@ -2404,15 +2352,9 @@ extern "C" int mc_bam_gpu_open_bases(const char* path, int device, int n_threads
     MC_REQUIRE(path && out, MC_E_INVALID, "null argument");
     *out = nullptr;
     MC_REQUIRE(min_mapq >= 0 && min_mapq <= 255, MC_E_INVALID, "min_mapq %d outside 0..255", min_mapq);
-    std::unique_ptr<mc_bam_gpu> g;
-    if (int rc = open_common(path, device, n_threads, flag_filter, g)) return rc;
-    g->bases_mode = true;
-    g->min_mapq = min_mapq;
-    const double t0 = now_s();
-    if (int rc = gpu_decode(g.get(), window_bytes)) return rc;
-    g->t_open = (now_s() - t0) * 1e3;
-    *out = g.release();
-    return MC_OK;
+    return open_with(path, device, n_threads, flag_filter, out,
+                     [&](mc_bam_gpu* g) { g->mode = Mode::Bases, g->min_mapq = min_mapq; },
+                     [&](mc_bam_gpu* g) { return gpu_decode(g, window_bytes); });
 }
 
 extern "C" int mc_bam_gpu_bases_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_tid, const int32_t** d_pos,
@@ -2423,7 +2365,7 @@ extern "C" int mc_bam_gpu_bases_device(const mc_bam_gpu* g, int64_t* n, const in
     MC_REQUIRE(g && n && d_tid && d_pos && d_cig_off && d_cigar && n_words && d_l_seq && d_seq_off && d_seq &&
                    seq_bytes && d_qual_off && d_qual && qual_bytes,
                MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     *n = g->n_kept;
     *d_tid = g->tid.p;
     *d_pos = g->pos.p;
@@ -2444,7 +2386,7 @@ extern "C" int mc_bam_gpu_bases_copy(const mc_bam_gpu* g, int32_t* tid, int32_t*
                                      uint32_t* cigar, int32_t* l_seq, int64_t* seq_off, uint8_t* seq,
                                      int64_t* qual_off, uint8_t* qual) {
     MC_REQUIRE(g && cig_off && seq_off && qual_off, MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     MC_REQUIRE(((tid && pos && l_seq) || !g->n_kept) && (cigar || !g->n_words) && (seq || !g->n_bytes) &&
                    (qual || !g->n_qual),
                MC_E_INVALID, "null argument");   // (an empty table: only the offsets' first entries)
@@ -2472,14 +2414,14 @@ extern "C" int mc_bam_gpu_bases_copy(const mc_bam_gpu* g, int32_t* tid, int32_t*
 
 extern "C" int mc_bam_gpu_bases_flags(const mc_bam_gpu* g, const uint16_t** d_flag) {
     MC_REQUIRE(g && d_flag, MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     *d_flag = g->bflag.p;
     return MC_OK;
 }
 
 extern "C" int mc_bam_gpu_bases_copy_flags(const mc_bam_gpu* g, uint16_t* flag) {
     MC_REQUIRE(g, MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     MC_REQUIRE(flag || !g->n_kept, MC_E_INVALID, "null argument");
     if (!g->n_kept) return MC_OK;
     HIP_TRY(hipSetDevice(g->device));
@@ -2490,14 +2432,14 @@ extern "C" int mc_bam_gpu_bases_copy_flags(const mc_bam_gpu* g, uint16_t* flag) 
 
 extern "C" int mc_bam_gpu_bases_mapq(const mc_bam_gpu* g, const uint8_t** d_mapq) {
     MC_REQUIRE(g && d_mapq, MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     *d_mapq = g->bmapq.p;
     return MC_OK;
 }
 
 extern "C" int mc_bam_gpu_bases_copy_mapq(const mc_bam_gpu* g, uint8_t* mapq) {
     MC_REQUIRE(g, MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     MC_REQUIRE(mapq || !g->n_kept, MC_E_INVALID, "null argument");
     if (!g->n_kept) return MC_OK;
     HIP_TRY(hipSetDevice(g->device));
@@ -2509,7 +2451,7 @@ extern "C" int mc_bam_gpu_bases_copy_mapq(const mc_bam_gpu* g, uint8_t* mapq) {
 extern "C" int mc_bam_gpu_bases_counts(const mc_bam_gpu* g, int64_t* records, int64_t* kept, int64_t* no_seq,
                                        int64_t* bad_cigar) {
     MC_REQUIRE(g && records && kept && no_seq && bad_cigar, MC_E_INVALID, "null argument");
-    MC_REQUIRE(g->bases_mode, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
+    MC_REQUIRE(g->mode == Mode::Bases, MC_E_STATE, "not a bases-mode decode (mc_bam_gpu_open_bases)");
     *records = g->hdr.n_records;
     *kept = g->b_passed;
     *no_seq = g->b_no_seq;
@@ -2526,7 +2468,7 @@ extern "C" int mc_bam_gpu_header(const mc_bam_gpu* g, const mc_bam** header) {
 extern "C" int mc_bam_gpu_intervals_device(const mc_bam_gpu* g, int64_t* n, const int32_t** d_tid,
                                            const int32_t** d_pos, const int32_t** d_span) {
     MC_REQUIRE(g && n && d_tid && d_pos && d_span, MC_E_INVALID, "null argument");
-    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
+    MC_REQUIRE(g->mode != Mode::Bases, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     *n = g->n_kept;
     *d_tid = g->tid.p;
     *d_pos = g->pos.p;
@@ -2536,7 +2478,7 @@ extern "C" int mc_bam_gpu_intervals_device(const mc_bam_gpu* g, int64_t* n, cons
 
 extern "C" int mc_bam_gpu_intervals(const mc_bam_gpu* g, int32_t* tid, int32_t* pos, int32_t* span) {
     MC_REQUIRE(g && tid && pos && span, MC_E_INVALID, "null argument");
-    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
+    MC_REQUIRE(g->mode != Mode::Bases, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     HIP_TRY(hipSetDevice(g->device));
     if (g->n_kept) {
         HIP_TRY(hipMemcpy(tid, g->tid.p, g->n_kept * 4, hipMemcpyDeviceToHost));
@@ -2610,14 +2552,8 @@ extern "C" int mc_bam_gpu_open_extents(const char* path, int device, int n_threa
     MC_REQUIRE(path && out && (ext || n_ref == 0) && n_ref >= 0 && n_sel >= 0 && (sel || n_sel == 0) &&
                    n_no_coor >= 0,
                MC_E_INVALID, "bad argument");
-    *out = nullptr;
-    std::unique_ptr<mc_bam_gpu> g;
-    if (int rc = open_common(path, device, n_threads, flag_filter, g)) return rc;
-    const double t0 = now_s();
-    if (int rc = gpu_decode_extents(g.get(), n_ref, ext, n_no_coor, n_sel, sel)) return rc;
-    g->t_open = (now_s() - t0) * 1e3;
-    *out = g.release();
-    return MC_OK;
+    return open_with(path, device, n_threads, flag_filter, out, [](mc_bam_gpu*) {},
+                     [&](mc_bam_gpu* g) { return gpu_decode_extents(g, n_ref, ext, n_no_coor, n_sel, sel); });
 }
 
 extern "C" int mc_bam_gpu_open_contigs(const char* path, const char* bai_path, int device, int n_threads,
@@ -2643,7 +2579,7 @@ extern "C" int mc_bam_gpu_open_contigs(const char* path, const char* bai_path, i
 
 extern "C" int mc_bam_gpu_extents(const mc_bam_gpu* g, int32_t n_ref, mc_contig_extent* ext, int64_t* n_no_coor) {
     MC_REQUIRE(g && (ext || n_ref == 0) && n_no_coor, MC_E_INVALID, "null argument");
-    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
+    MC_REQUIRE(g->mode != Mode::Bases, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     MC_REQUIRE(n_ref == (int32_t)g->hdr.names.size(), MC_E_INVALID, "the file has %zu contigs, not %d",
                g->hdr.names.size(), n_ref);
     HIP_TRY(hipSetDevice(g->device));
@@ -2750,7 +2686,7 @@ extern "C" int mc_bam_gpu_restrict(mc_bam_gpu* g, int32_t n_sel, const int32_t* 
 extern "C" int mc_bam_gpu_intervals_range(const mc_bam_gpu* g, int64_t first, int64_t count, int32_t* tid,
                                           int32_t* pos, int32_t* span) {
     MC_REQUIRE(g && tid && pos && span, MC_E_INVALID, "null argument");
-    MC_REQUIRE(!g->bases_mode, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
+    MC_REQUIRE(g->mode != Mode::Bases, MC_E_STATE, "a bases-mode decode (mc_bam_gpu_open_bases) has no intervals");
     MC_REQUIRE(first >= 0 && count >= 0 && first + count <= g->n_kept, MC_E_RANGE,
                "intervals [%lld, %lld) outside the %lld kept", (long long)first, (long long)(first + count),
                (long long)g->n_kept);

@@ -591,6 +591,117 @@ def test_gpu_decode_near_valid_records(lib_built, tmp_path, good_bins, ascending
         assert t["parse_rounds"] < 4, t
 
 
+def _open_mode(mode, path, window=0):
+    """A raw decode handle of one of the four record modes (the caller closes it)."""
+    lib, p, g = _lib(), path.encode(), ctypes.c_void_p()
+    from metacov_amd import _lib as L
+    rc = {"intervals": lambda: lib.mc_bam_gpu_open(p, 0, 0, 0x704, window, ctypes.byref(g)),
+          "scan": lambda: lib.mc_bam_gpu_open_scan(p, 0, 0, window, ctypes.byref(g)),
+          "reads": lambda: lib.mc_bam_gpu_open_reads(p, 0, 0, 5, window, ctypes.byref(g)),
+          "bases": lambda: lib.mc_bam_gpu_open_bases(p, 0, 0, 0x704, 0, window, ctypes.byref(g))}[mode]()
+    L.check(rc, lib)
+    return g
+
+
+MODES = ("intervals", "scan", "reads", "bases")
+
+
+def _mode_stats(mode, path):
+    from metacov_amd import _lib as L
+    lib, g = _lib(), _open_mode(mode, path)
+    t = L.GpuDecodeTimings()
+    try:
+        L.check(lib.mc_bam_gpu_stats(g, ctypes.byref(t)), lib)
+    finally:
+        lib.mc_bam_gpu_close(g)
+    return {k: getattr(t, k) for k in ("resyncs", "parse_rounds", "resync_passes")}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ascending", [True, False])
+def test_gpu_decode_false_syncs_every_mode(lib_built, tmp_path, ascending):
+    """Fake records with right bins make most segment syncs of this file
+    false (counted here on the CPU with the sync's own rule), and the rounds
+    of parse_window correct them from each walk's landing.  The landing
+    depends only on the record framing, which the four modes share: each
+    mode's decode equals its host source, and all four take the same rounds."""
+    from metacov_amd import bases as mb, experimental as mx, scan as mscan
+    from metacov_amd.bam import GpuBamFile
+    from tests import bases_model as bm
+    p = str(tmp_path / "nv.bam")
+    _near_valid_bam(p, 8000, good_bins=True, ascending=ascending, fakes=12)
+    data, o, n_ref = _inflated(p)
+    real = set(_record_starts(data, o))
+    seg = 64 << 10
+    nseg = (len(data) - o + seg - 1) // seg
+    false_syncs = 0
+    for i in range(1, nseg):
+        cut = o + i * seg
+        q = next((q for q in range(cut, min(cut + seg, len(data))) if _chain(data, q, n_ref) == 1), None)
+        false_syncs += q is not None and q not in real
+    assert nseg > 8 and false_syncs >= 8, (nseg, false_syncs)
+
+    with GpuBamFile(p) as g:
+        _assert_oracle(p, g)
+    outs = []
+    for decode in ("host", "gpu"):
+        c = mscan.ByFlag([mscan.BaseHist(2), mscan.KmerHist(5, 6, 4, 1), mscan.MirrorHist(4, 10),
+                          mscan.IsizeHist()], [mscan.Flags["IsRead1"], mscan.Flags["Readdir"]])
+        n = mscan.scan_reads(p, None, c, decode=decode)
+        outs.append((n, [[list(map(str, r)) for r in q.get_rows()] for grp in c.processors for q in grp.processors]))
+    assert outs[0][0] == outs[1][0] == 8000 and outs[0][1] == outs[1][1]
+    with mx.ReadTable(p, 5, decode="host") as h, mx.ReadTable(p, 5, decode="gpu") as g:
+        assert (h.references, h.lengths, h.n_records, h.n_placed) == \
+            (g.references, g.lengths, g.n_records, g.n_placed)
+        fh, fg = h.fields(), g.fields()
+        for key in fh:
+            if isinstance(fh[key], list):
+                assert fh[key] == fg[key], key
+            else:
+                np.testing.assert_array_equal(fh[key], fg[key], err_msg=key)
+    _, _, want, counts = bm.kept_reads(p)
+    with mb.GpuBaseSource(p, 0) as src:
+        assert src.counts() == counts and len(src) == bm.n_reads(want) == 8000
+        got = src.copy()
+        for k in want:
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k
+
+    stats = {m: _mode_stats(m, p) for m in MODES}
+    for m in MODES:
+        assert stats[m]["resyncs"] >= 1 and stats[m]["parse_rounds"] < 4, (m, stats[m])
+        assert stats[m] == stats["intervals"], stats
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("window", [0, 1 << 18])
+def test_gpu_decode_error_texts_every_mode(lib_built, tmp_path, window):
+    """A stream cut inside its last record and a record size below the fixed
+    fields are refused by the walk's frame with the same text in every mode
+    (one segment: nothing to resync).  The resident decode's offsets are the
+    inflated stream's; a windowed decode's are relative to its window buffer,
+    so only the error class is pinned there."""
+    p = str(tmp_path / "ok.bam")
+    recs = [synth.SynthRecord("r%d" % j, j % 2, 10 + 3 * j, 0, [(0, 50)], 50) for j in range(300)]
+    recs.sort(key=lambda r: (r.tid, r.pos))
+    synth.write_bam(p, ["a", "b"], [5000, 5000], recs)
+    data, o, _ = _inflated(p)
+    starts = _record_starts(data, o)
+    assert len(starts) == 300 and len(data) < (64 << 10) and len(data) - starts[-1] > 37
+    cut, bad = str(tmp_path / "cut.bam"), str(tmp_path / "bad.bam")
+    with open(cut, "wb") as fh:
+        fh.write(synth._bgzf(data[:len(data) - 37]))
+    q = starts[150]
+    with open(bad, "wb") as fh:
+        fh.write(synth._bgzf(data[:q] + struct.pack("<i", 8) + data[q + 4:]))
+    for mode in MODES:
+        _lib().mc_bam_gpu_close(_open_mode(mode, p, window))     # (the unmodified stream decodes)
+        for path, text, at in ((cut, "truncated record", starts[-1]), (bad, "bad record size", q)):
+            want = text if window else "%s at byte %d of the inflated stream" % (text, at)
+            with pytest.raises(MetacovError) as e:
+                _open_mode(mode, path, window)
+            assert want in str(e.value), (mode, str(e.value))
+
+
 # ------------------------------------------------ contig shards (SURVEY §8e)
 
 def _multi_contig_bam(tmp_path, n_reads=300_000, seed=21):
