@@ -703,6 +703,68 @@ int mc_bases_consensus_device(const mc_bases* h, const uint8_t** d_aligned, cons
 int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, float* scan_ms, float* emit_ms);
 int mc_bases_set(mc_bases* h, int64_t first, int64_t count, const uint32_t* in /* 6 x count */);
 
+/* Diversity (mc_bases_diversity), a further stage over the planes on the
+ * device: per window the sums a metagenome user derives breadth, mean base
+ * depth, SNV density, nucleotide diversity and the identity to the reference
+ * from (inStrain's conANI and popANI).  MC_DIV_COLS int64 per window, all
+ * integer, exact and independent of order.
+ *
+ * Windows are mc_windows_compute's, over the handle's segments: segment s of
+ * length L = seg_off[s + 1] - seg_off[s] is cut into the windows [k * window,
+ * min((k + 1) * window, L)) of its plane indices; window == 0 is one window
+ * per non-empty segment; an empty segment owns none.  Segment s owns rows
+ * [win_first[s], win_first[s + 1]) (mc_bases_diversity_first, arithmetic);
+ * *n_windows = win_first[S] (more than 2^31: MC_E_RANGE).  window is 0 or at
+ * least MC_DIV_MIN_WINDOW, else MC_E_INVALID.
+ *
+ * At plane index i let a[0..3] be the A, C, G, T counts and n = a0 + a1 + a2 +
+ * a3 in 64 bits (DEL and N are ignored: a deletion is not a base), r = ref[i]
+ * as mc_bases_sites takes it (0..3 = A/C/G/T; anything else, or ref == NULL,
+ * unknown), md = max(min_depth, 2), mc = max(min_count, 1), qualifies(x) =
+ * x >= mc and x * 10^6 >= min_ppm * n in 64-bit integers, major the first
+ * maximum of a in channel order, minor the largest of the other three counts.
+ * A position is covered iff n >= md.  The columns:
+ *   0 positions  the window's length
+ *   1 covered    covered positions
+ *   2 bases      sum of n over ALL the window's positions
+ *   3 snv        covered positions with qualifies(minor)
+ *   4 pi_fix     sum over the covered positions of q, below
+ *   5 compared   covered positions with r known
+ *   6 con_diff   of those, major != r
+ *   7 pop_diff   of those, major != r and not qualifies(a[r])
+ * so that pi = pi_fix / 2^32 / covered, conANI = 1 - con_diff / compared and
+ * popANI = 1 - pop_diff / compared.  q is the unbiased pairwise estimator (Nei
+ * and Li) in 32.32 fixed point: num = n^2 - sum a_c^2, den = n (n - 1), both
+ * exact in uint64, q = llrint((double)num / (double)den * 2^32): one IEEE
+ * double division, round half to even; q = 0 where num == 0.  Both
+ * conversions are exact while n < 2^26, and q <= 2^32.  A covered position
+ * with n >= 2^26 fails the call with MC_E_RANGE (mc_last_error names the
+ * lowest such plane index) and no result becomes current.
+ *
+ * Errors: before begin, and _first / _get / _device / _timing without a
+ * current result, MC_E_STATE; negative thresholds, min_ppm > 10^6, window in
+ * 1..15 and a _get range outside [0, n_windows], MC_E_INVALID.  The rows stay
+ * in device memory owned by the handle (buffers only grow;
+ * mc_bases_diversity_device exposes them) until the next mc_bases_diversity,
+ * _add_batch, _set, _ins_set or _begin; they share nothing with the sites,
+ * consensus or insertion buffers, so those results survive a diversity call
+ * and the other way round.  Strand, quality and insertion tracking do not
+ * change a row.  Device side (csrc/bases_div.h): one workgroup per tile sums
+ * the columns per window in LDS (wave reductions where a wave's positions lie
+ * in one or two windows, LDS adds otherwise); the rows of windows inside a
+ * tile are stored, the first and the last window of a tile, which neighbours
+ * may share, are zeroed by a launch in front (combine_ms of
+ * mc_bases_diversity_timing; tile_ms is the tile kernel's) and added with
+ * 64-bit integer atomics.  No floating-point atomics. */
+#define MC_DIV_COLS 8
+#define MC_DIV_MIN_WINDOW 16
+int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                       const uint8_t* ref /* N, or NULL */, int64_t* n_windows);
+int mc_bases_diversity_first(const mc_bases* h, int64_t* win_first /* S + 1 */);
+int mc_bases_diversity_get(const mc_bases* h, int64_t first, int64_t count, int64_t* rows /* count x 8 */);
+int mc_bases_diversity_device(const mc_bases* h, const int64_t** d_rows, int64_t* n_windows);
+int mc_bases_diversity_timing(const mc_bases* h, float* tile_ms, float* combine_ms);
+
 /* Insertion alleles (csrc/bases_ins.h), an opt-in stage of mc_bases, off by
  * default: with it off no launch, byte or error of the calls above changes.
  * The reference has nothing here; the contract is this library's own.

@@ -157,6 +157,71 @@ class Consensus:
         return self._bc.consensus_letters(True, int(self.first[s]), int(self.first[s + 1] - self.first[s]))
 
 
+DIV_COLS = 8                        # MC_DIV_COLS
+DIV_MIN_WINDOW = 16                 # MC_DIV_MIN_WINDOW
+DIV_COLUMNS = ("positions", "covered", "bases", "snv", "pi_fix", "compared", "con_diff", "pop_diff")
+PI_ONE = 4294967296.0               # pi_fix is 32.32 fixed point
+
+
+def _ratio(num, den):
+    """num / den as float64, NaN where den is 0."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    out = np.full(num.shape, np.nan)
+    np.divide(num, den, out=out, where=den != 0)
+    return out
+
+
+class Diversity:
+    """The diversity rows of S segments (BaseCounter.diversity): segment s owns
+    rows win_first[s] .. win_first[s + 1], its windows in order; rows [n, 8]
+    int64 with the columns DIV_COLUMNS, each also an attribute (positions,
+    covered, bases, snv, pi_fix, compared, con_diff, pop_diff).  window: the
+    window length asked for (0: whole segments).  The ratio methods return
+    float64 with NaN where the denominator is 0."""
+
+    def __init__(self, win_first, rows, window=0):
+        self.win_first = np.asarray(win_first, np.int64)
+        self.rows = np.asarray(rows, np.int64).reshape(-1, DIV_COLS)
+        self.window = int(window)
+        for c, name in enumerate(DIV_COLUMNS):
+            setattr(self, name, self.rows[:, c])
+
+    def __len__(self):
+        return len(self.rows)
+
+    def segment(self):
+        """int64 [n]: the segment of each row."""
+        return np.repeat(np.arange(len(self.win_first) - 1, dtype=np.int64), np.diff(self.win_first))
+
+    def start(self):
+        """int64 [n]: each window's first position, counted from its segment's start."""
+        k = np.arange(len(self.rows), dtype=np.int64) - self.win_first[:-1][self.segment()]
+        return k * self.window
+
+    def end(self):
+        return self.start() + self.positions
+
+    def pi(self):
+        """Nucleotide diversity: the mean over the covered positions."""
+        return _ratio(self.pi_fix / PI_ONE, self.covered)
+
+    def breadth(self):
+        return _ratio(self.covered, self.positions)
+
+    def mean_depth(self):
+        """Mean A + C + G + T over all the window's positions."""
+        return _ratio(self.bases, self.positions)
+
+    def snv_density(self):
+        return _ratio(self.snv, self.covered)
+
+    def con_ani(self):
+        return 1.0 - _ratio(self.con_diff, self.compared)
+
+    def pop_ani(self):
+        return 1.0 - _ratio(self.pop_diff, self.compared)
+
+
 class BaseSource:
     """One mc_bases_src: the kept records of a coordinate-sorted BAM."""
 
@@ -697,6 +762,32 @@ class BaseCounter:
               self._lib)
         return {"call_ms": a.value, "scan_ms": b.value, "emit_ms": c.value}
 
+    def diversity(self, window=0, min_depth=2, min_count=1, min_ppm=0, ref=None):
+        """Per window of `window` positions of each segment (0: per segment)
+        the eight sums of the header's "Diversity", reduced on the device;
+        ref: optional uint8 [N] codes as sites takes them.  Returns a
+        Diversity."""
+        if ref is not None:
+            ref = np.ascontiguousarray(ref, dtype=np.uint8)
+            if len(ref) != int(self.seg_off[-1]):
+                raise ValueError("the reference plane must have one entry per position")
+        n = ctypes.c_int64()
+        check(self._lib.mc_bases_diversity(self._h, int(window), int(min_depth), int(min_count), int(min_ppm),
+                                           ptr(ref), ctypes.byref(n)), self._lib)
+        n = n.value
+        first = np.zeros(self._S + 1, np.int64)
+        check(self._lib.mc_bases_diversity_first(self._h, ptr(first)), self._lib)
+        rows = np.zeros((n, DIV_COLS), np.int64)
+        check(self._lib.mc_bases_diversity_get(self._h, 0, n, ptr(rows)), self._lib)
+        return Diversity(first, rows, window)
+
+    def diversity_timing(self):
+        """HIP-event times of the last diversity call: the tile kernel, and
+        the launch in front of it that zeroes the rows tiles share."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        check(self._lib.mc_bases_diversity_timing(self._h, ctypes.byref(a), ctypes.byref(b)), self._lib)
+        return {"tile_ms": a.value, "combine_ms": b.value}
+
     def timing(self):
         a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         t, r = ctypes.c_int64(), ctypes.c_int64()
@@ -846,6 +937,68 @@ def write_consensus_summary(fh, names, starts, ends, summary, header=True, inser
     for name, a, b, row in zip(names, starts, ends, summary.tolist()):
         fh.write("%s\t%d\t%d\t%s\n" % (name, int(a), int(b), "\t".join(str(v) for v in row)))
     return len(summary)
+
+
+DIVERSITY_HEADER = ("#contig\tstart\tend\tpositions\tcovered\tbases\tsnv\tpi\tcompared\tcon_diff\tpop_diff\t"
+                    "con_ani\tpop_ani\n")
+
+
+def write_diversity(fh, names, starts, diversity, header=True):
+    """Tab-separated `contig start end positions covered bases snv pi compared
+    con_diff pop_diff con_ani pop_ani`, one line per window: names and starts
+    per segment (start, end 0-based, half-open, in the contig's coordinates);
+    the integers as they are, pi and the two identities '%.6f', or NA where
+    their denominator is 0.  Returns the lines written."""
+    if header:
+        fh.write(DIVERSITY_HEADER)
+    d = diversity
+    seg = d.segment()
+    a = d.start() + np.asarray(starts, np.int64).reshape(-1)[seg] if len(d) else np.zeros(0, np.int64)
+    b = a + d.positions
+
+    def fmt(v):
+        return "NA" if np.isnan(v) else "%.6f" % v
+
+    pi, con, pop = d.pi(), d.con_ani(), d.pop_ani()
+    for k, row in enumerate(d.rows.tolist()):
+        fh.write("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%s\t%s\n" % (
+            names[int(seg[k])], int(a[k]), int(b[k]), row[0], row[1], row[2], row[3], fmt(pi[k]), row[5], row[6],
+            row[7], fmt(con[k]), fmt(pop[k])))
+    return len(d)
+
+
+def diversity(path, contig, start=None, stop=None, window=0, quality_threshold=0, min_mapq=0, min_depth=2,
+              min_count=1, min_ppm=0, ref=None, device=0, decode="host"):
+    """The diversity rows of [start, stop) of one contig (default: all of it)
+    in one call: a Diversity of one segment, cut into windows of `window`
+    positions (0: one row).  ref: optional ASCII letters (str, bytes or uint8)
+    of the same range.  decode: as add_bam."""
+    if decode not in ("host", "gpu"):
+        raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
+    if window != 0 and window < DIV_MIN_WINDOW:
+        raise ValueError("window must be 0 or at least %d" % DIV_MIN_WINDOW)
+    lib = _lib.load()
+    with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
+        names = [w.split()[0] if w.split() else w for w in src.references]
+        if contig not in names:
+            raise KeyError("contig '%s' is not in the header of %s" % (contig, path))
+        tid = names.index(contig)
+        length = src.lengths[tid]
+    start = 0 if start is None else int(start)
+    stop = length if stop is None else int(stop)
+    if start < 0 or stop < start:
+        raise ValueError("bad range [%d, %d)" % (start, stop))
+    codes = None
+    if ref is not None:
+        if isinstance(ref, str):
+            ref = ref.encode("ascii")
+        codes = ref_codes(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref)
+        if len(codes) != stop - start:
+            raise ValueError("ref must have stop - start letters")
+    with BaseCounter(len(names), device, lib) as bc:
+        bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
+        bc.add_bam(path, min_mapq=min_mapq, decode=decode)
+        return bc.diversity(window, min_depth, min_count, min_ppm, codes)
 
 
 def consensus(path, contig, start=None, stop=None, quality_threshold=0, min_mapq=0, min_depth=1, min_count=1,

@@ -59,6 +59,17 @@ writes one FASTA record per contig or region, called per position from the
 same counts on the GPU: the strongest of A, C, G, T and deletion if it passes
 the thresholds, else N.  It never contains inserted bases.
 
+Diversity (no counterpart in the reference either):
+
+    python -m metacov_amd.cli diversity -b X.bam [-o out.tsv] [--by N] [-f ref.fa] [--min-baseq 0] [--min-mapq 0]
+                                        [--min-depth 5] [--min-count 2] [--min-frac 0.05]
+                                        [-rc R.csv | -rb R.blast7] [--decode host|gpu]
+
+writes per contig, region or fixed window the covered positions, the base
+sum, the SNV count, the nucleotide diversity pi and, with `-f`, the consensus
+and population identity to the reference (conANI, popANI), reduced on the GPU
+from the same counts to one row per window (csrc/bases_div.h).
+
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
     python -m torch.distributed.run --nproc-per-node 8 -m metacov_amd.cli pileup -b X.bam ...
@@ -1125,6 +1136,126 @@ def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_c
         log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
                  "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
     log.info("%d sequences written", n)
+    if err is not None:      # the regions before a failing one are written first, as pileup does
+        raise err
+
+
+def write_diversity(path, references, tids, starts, ends, outfile, fasta=None, device=0, by=0, min_baseq=0,
+                    min_mapq=0, min_depth=5, min_count=2, min_ppm=50000, decode="host"):
+    """The diversity table of the segments (header contig ids), group by group
+    as write_bases does it, each written before the next is computed: one line
+    per segment, or per window of `by` positions.  Returns (lines written, the
+    source's record counts)."""
+    from . import bases as _bases
+    import contextlib
+    names = [w.split()[0] if w.split() else w for w in references]
+    outfile.write(_bases.DIVERSITY_HEADER)
+    written, counts = 0, None
+    if len(tids) == 0:
+        return 0, None
+    fa = _experimental.FastaFile(fasta) if fasta else None
+    with contextlib.ExitStack() as stack:
+        bc = stack.enter_context(_bases.BaseCounter(len(references), device))
+        src = None
+        if decode == "gpu":
+            try:
+                src = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
+            except _bases._lib.MetacovError as e:
+                if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
+                    raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
+                                               "run with --decode host (%s)" % (path, device, e))
+                raise
+        for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
+            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
+            if src is not None:
+                bc.add_device(src)
+                counts = src.counts()
+            else:
+                counts = bc.add_bam(path, min_mapq=min_mapq)
+            codes = None
+            if fa is not None:
+                codes = _bases.ref_codes(np.concatenate(
+                    [_segment_letters(fa, names[int(tids[i])], starts[i], ends[i]) for i in range(a, b)] +
+                    [np.zeros(0, np.uint8)]))
+            div = bc.diversity(by, min_depth, min_count, min_ppm, codes)
+            written += _bases.write_diversity(outfile, [names[int(t)] for t in tids[a:b]], starts[a:b], div,
+                                              header=False)
+    return written, counts
+
+
+@main.command()
+@click.option('--bamfile', '-b', type=click.File('rb'), required=True,
+              help="Input BAM file. Must be coordinate-sorted.")
+@click.option('--outfile', '-o', type=click.File('w'), default="-",
+              help="Output table (default STDOUT)")
+@click.option('--by', type=int, default=0, metavar="N",
+              help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
+@click.option('--reference-fasta', '-f', type=click.File('rb'),
+              help="Reference FASTA (plain or gzip): fills compared, con_diff, pop_diff and the two identities")
+@click.option('--min-baseq', type=click.IntRange(0), default=0,
+              help="Count only bases of at least this quality")
+@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
+              help="Use only reads of at least this mapping quality")
+@click.option('--min-depth', type=click.IntRange(0), default=5, show_default=True,
+              help="A position is covered with A + C + G + T of at least this (never below 2)")
+@click.option('--min-count', type=click.IntRange(0), default=2, show_default=True,
+              help="An allele is present in the population with this many reads ...")
+@click.option('--min-frac', type=float, default=0.05, show_default=True,
+              help="... and this fraction (0..1) of the position's bases")
+@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
+              help="Input Region file in BLAST7 format")
+@click.option('--regionfile-csv', '-rc', type=click.File('r'),
+              help="Input Region file in CSV format")
+@click.option('--device', type=int, default=0, help="HIP device ordinal")
+@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
+              help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
+                   "the GPU, the records staying in device memory (the file's reads must fit there)")
+def diversity(bamfile, outfile, by, reference_fasta, min_baseq, min_mapq, min_depth, min_count, min_frac,
+              regionfile_blast7, regionfile_csv, device, decode):
+    """
+    Write windowed nucleotide diversity, SNV counts and identity to the reference
+
+    One line `contig start end positions covered bases snv pi compared
+    con_diff pop_diff con_ani pop_ani` per contig in header order, or per
+    region of a region file in file order, whole (--by 0) or cut into windows
+    of N positions.  covered: positions with at least --min-depth bases; snv:
+    covered positions whose second allele passes --min-count and --min-frac;
+    pi: the mean unbiased pairwise diversity of the covered positions.  With
+    -f, con_ani is the share of the covered positions whose major allele is
+    the reference base, pop_ani the share where the reference base is the
+    major allele or passes the two thresholds; without it both are NA.
+    Deletions are not bases here.  Reduced on the GPU; single process only.
+    """
+    from . import bases as _bases
+    if regionfile_blast7 and regionfile_csv:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    if by != 0 and by < _bases.DIV_MIN_WINDOW:
+        raise click.BadParameter("must be 0 or at least %d" % _bases.DIV_MIN_WINDOW, param_hint="--by")
+    if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
+        raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
+    min_ppm = int(round(min_frac * 1e6))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("diversity runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)")
+    fasta = reference_fasta.name if reference_fasta else None
+    with _bases.BaseSource(bamfile.name) as head:
+        references, lengths = list(head.references), list(head.lengths)
+    err = None
+    if regionfile_blast7 or regionfile_csv:
+        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
+        _, tids, starts, ends, err = resolve_regions(head, regions)
+    else:
+        tids = np.arange(len(lengths), dtype=np.int32)
+        starts = np.zeros(len(tids), np.int64)
+        ends = np.asarray(lengths, np.int64)
+    n, counts = write_diversity(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
+                                by=by, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
+                                min_count=min_count, min_ppm=min_ppm, decode=decode)
+    outfile.flush()
+    if counts:
+        log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
+                 "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    log.info("%d windows written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err
 

@@ -828,6 +828,7 @@ __global__ __launch_bounds__(kThreads) void cons_emit_kernel(const uint8_t* __re
 }
 
 #include "bases_ins.h"   // the insertion stage's kernels
+#include "bases_div.h"   // the diversity stage's kernels
 
 constexpr size_t kArenaPad = 64;   // bytes behind every uploaded array
 
@@ -892,6 +893,16 @@ struct mc_bases {
     Buf<int32_t> cons_cols;              // [8][T]
     Buf<int64_t> cons_pre, cons_first, cons_rows;   // [8][T + 1], [S + 1], [S][8]
     float ms_cons_call = 0, ms_cons_scan = 0, ms_cons_emit = 0;
+    // diversity: buffers of its own again, so its rows live beside sites and a consensus
+    bool have_div = false;
+    int64_t n_div = 0;                   // windows in all
+    std::vector<int64_t> div_first;      // [S + 1]
+    hipEvent_t dev[3] = {nullptr, nullptr, nullptr};
+    Buf<uint8_t> div_ref;
+    Buf<DivTile> div_tiles;              // [T]
+    Buf<int64_t> div_rows;               // [n_div][8]
+    Buf<unsigned long long> div_bad;     // the lowest covered plane index with 2^26 bases or more (pin[7] on the host)
+    float ms_div_tile = 0, ms_div_zero = 0;
     // insertions (opt-in, mc_bases_track_insertions): events, their sorted buckets, two row tables
     bool track_next = false, tracking = false;
     bool ins_from_set = false;           // mc_bases_ins_set installed the sorted buckets
@@ -930,6 +941,8 @@ struct mc_bases {
         for (auto& e : ev)
             if (e) (void)hipEventDestroy(e);
         for (auto& e : cev)
+            if (e) (void)hipEventDestroy(e);
+        for (auto& e : dev)
             if (e) (void)hipEventDestroy(e);
         if (pin) (void)hipHostFree(pin);
         if (stream) (void)hipStreamDestroy(stream);
@@ -974,6 +987,7 @@ void invalidate_ins(mc_bases* h) {
 void invalidate_results(mc_bases* h) {
     h->have_sites = false;
     h->have_cons = false;
+    h->have_div = false;
     invalidate_ins(h);
 }
 
@@ -995,6 +1009,7 @@ extern "C" int mc_bases_create(int device, int32_t n_ref, mc_bases** out) {
               h->flags.reserve(2) == hipSuccess;
     for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     for (auto& e : h->cev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (auto& e : h->dev) ok = ok && hipEventCreate(&e) == hipSuccess;
     for (auto& e : h->iev) ok = ok && hipEventCreate(&e) == hipSuccess;
     if (!ok) {
         delete h;
@@ -1031,6 +1046,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->have_sites = false;
     h->have_cons = false;
     h->have_cons_ins = false;
+    h->have_div = false;
     h->tracking = false;
     h->strand = false;
     h->have_sites_rev = false;
@@ -1127,6 +1143,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->n_reads = 0;
     h->ms_prepass = h->ms_pileup = h->ms_sites = 0;
     h->ms_cons_call = h->ms_cons_scan = h->ms_cons_emit = 0;
+    h->ms_div_tile = h->ms_div_zero = 0;
     h->begun = true;
     return MC_OK;
 }
@@ -2072,6 +2089,121 @@ extern "C" int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, floa
     return MC_OK;
 }
 
+// ---- diversity (the contract is the header's, "Diversity") --------------------
+
+extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth, int64_t min_count, int64_t min_ppm,
+                                  const uint8_t* ref, int64_t* n_windows) {
+    MC_REQUIRE(h && n_windows, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->begun, MC_E_STATE, "no segments (call mc_bases_begin)");
+    MC_REQUIRE(min_depth >= 0 && min_count >= 0 && min_ppm >= 0 && min_ppm <= 1000000, MC_E_INVALID,
+               "diversity thresholds out of range (min_depth %lld, min_count %lld, min_ppm %lld of 10^6)",
+               (long long)min_depth, (long long)min_count, (long long)min_ppm);
+    MC_REQUIRE(window == 0 || window >= MC_DIV_MIN_WINDOW, MC_E_INVALID, "window %lld: must be 0 or at least %d",
+               (long long)window, MC_DIV_MIN_WINDOW);
+    h->have_div = false;
+    const int64_t T = h->n_tiles, S = h->S;
+    // the windows (arithmetic) and, per tile, its first window and where in it the tile starts: the tile
+    // table again, as mc_bases_begin cut it from the segments' lengths
+    std::vector<int64_t> first((size_t)S + 1);
+    std::vector<DivTile> dt;
+    dt.reserve((size_t)T);
+    int64_t nw = 0;
+    for (int64_t s = 0; s < S; ++s) {
+        first[(size_t)s] = nw;
+        const int64_t a = h->seg_off[(size_t)s], len = h->seg_off[(size_t)s + 1] - a;
+        for (int64_t p = 0; p < len;) {
+            const int64_t n = std::min<int64_t>(kTile - ((a + p) & 3), len - p);
+            dt.push_back(window ? DivTile{nw + p / window, p % window} : DivTile{nw, p});
+            p += n;
+        }
+        nw += window ? (len + window - 1) / window : (len > 0);
+        MC_REQUIRE(nw <= (int64_t(1) << 31), MC_E_RANGE, "more than 2^31 windows of %lld positions",
+                   (long long)window);
+    }
+    first[(size_t)S] = nw;
+    MC_REQUIRE((int64_t)dt.size() == T, MC_E_STATE, "tile table of %lld entries, %lld expected", (long long)dt.size(),
+               (long long)T);
+    const DivArgs da{(unsigned long long)std::max<int64_t>(min_depth, 2),
+                     (unsigned long long)std::max<int64_t>(min_count, 1), (unsigned long long)min_ppm,
+                     window ? window : 2 * kMaxPos};
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(h->div_tiles.reserve((size_t)T));
+    HIP_TRY(h->div_rows.reserve((size_t)(nw * kDivCols)));
+    HIP_TRY(h->div_bad.reserve(1));
+    hipStream_t st = h->stream;
+    const uint8_t* d_ref = nullptr;
+    if (ref && h->N) {
+        HIP_TRY(h->div_ref.reserve((size_t)h->N));
+        HIP_TRY(hipMemcpyAsync(h->div_ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, st));
+        d_ref = h->div_ref.p;
+    }
+    h->pin[7] = kNoBad;
+    HIP_TRY(hipMemcpyAsync(h->div_bad.p, h->pin + 7, 8, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(h->div_tiles.p, dt.data(), (size_t)T * sizeof(DivTile), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(h->dev[0], st));
+    if (T) {
+        hipLaunchKernelGGL(div_zero_kernel, dim3((unsigned)((T * 16 + 255) / 256)), dim3(256), 0, st, h->tiles.p,
+                           h->div_tiles.p, T, da.window, h->div_rows.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->dev[1], st));
+    if (T) {
+        hipLaunchKernelGGL(div_tile_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
+                           h->tiles.p, h->div_tiles.p, da, h->div_rows.p, h->div_bad.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(h->dev[2], st));
+    HIP_TRY(hipMemcpyAsync(h->pin + 7, h->div_bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));            // (dt is released)
+    const unsigned long long bad = h->pin[7];
+    MC_REQUIRE(bad == kNoBad, MC_E_RANGE,
+               "plane index %llu: A + C + G + T of a covered position is 2^26 or more (pi_fix is exact below that)",
+               bad);
+    HIP_TRY(hipEventElapsedTime(&h->ms_div_zero, h->dev[0], h->dev[1]));
+    HIP_TRY(hipEventElapsedTime(&h->ms_div_tile, h->dev[1], h->dev[2]));
+    h->div_first = std::move(first);
+    h->n_div = nw;
+    h->have_div = true;
+    *n_windows = nw;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_diversity_first(const mc_bases* h, int64_t* win_first) {
+    MC_REQUIRE(h && win_first, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
+    std::memcpy(win_first, h->div_first.data(), h->div_first.size() * 8);
+    return MC_OK;
+}
+
+extern "C" int mc_bases_diversity_get(const mc_bases* h, int64_t first, int64_t count, int64_t* rows) {
+    MC_REQUIRE(h, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
+    if (int rc = check_range(first, count, h->n_div, "windows")) return rc;
+    MC_REQUIRE(count == 0 || rows, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(rows, h->div_rows.p + first * kDivCols, (size_t)count * kDivCols * 8,
+                           hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_diversity_device(const mc_bases* h, const int64_t** d_rows, int64_t* n_windows) {
+    MC_REQUIRE(h && d_rows && n_windows, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
+    *d_rows = h->div_rows.p;
+    *n_windows = h->n_div;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_diversity_timing(const mc_bases* h, float* tile_ms, float* combine_ms) {
+    MC_REQUIRE(h && tile_ms && combine_ms, MC_E_INVALID, "null argument");
+    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
+    *tile_ms = h->ms_div_tile;
+    *combine_ms = h->ms_div_zero;
+    return MC_OK;
+}
+
 // ---- insertion alleles (the contract is the header's, "Insertion alleles") ----
 
 extern "C" int mc_bases_track_insertions(mc_bases* h, int on) {
@@ -2185,6 +2317,7 @@ extern "C" int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const 
     h->sorted_valid = false;
     invalidate_ins(h);
     h->have_cons = false;
+    h->have_div = false;
     HIP_TRY(h->ins_sorted.reserve((size_t)n));
     HIP_TRY(h->ins_weight.reserve((size_t)n));
     HIP_TRY(h->ins_bbase.reserve((size_t)T + 1));
