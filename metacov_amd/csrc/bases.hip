@@ -37,13 +37,13 @@
 //                         with plain load-add-store: a tile has one owner in
 //                         a launch and the launches of successive batches
 //                         are ordered on the stream.  No global atomics.
-//   bases_pileup_strand_kernel   the same walk on a handle that tracks strand
+//   bases_pileup_kernel<kModeStrand>   the same walk on a handle that tracks strand
 //                         (pileup_tile<true>): the reads' flags beside their
 //                         other words, forward and reverse counts in the two
 //                         16-bit halves of the same LDS words (two 32-bit
 //                         walks for a tile with more than 65535 reads), the
 //                         flush into the totals and the reverse planes.
-//   bases_pileup_quality_kernel  the same walk on a handle that tracks quality
+//   bases_pileup_kernel<kModeQuality>  the same walk on a handle that tracks quality
 //                         (pileup_tile<kModeQuality>): the reads' MAPQ bytes
 //                         beside their other words, one 64-bit LDS add per
 //                         counted base (count, quality byte, MAPQ in 16 + 24 +
@@ -91,7 +91,7 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kTile = 2048;                         // positions per tile: 6 x 4 B x 2048 = 48 KiB of LDS
 constexpr int kPlanes = 6;                          // A, C, G, T, N, DEL
 constexpr int kRounds = kTile / kThreads;           // positions per thread of the sites kernels
-constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_runs_compute's bound
+using mc::kMaxPos;
 constexpr unsigned long long kNoBad = ~0ull;
 constexpr uint32_t kQueryOps = 0x193u;              // M I S = X advance the query
 constexpr uint32_t kRefOps = 0x18Du;                // M D N = X advance the reference
@@ -401,41 +401,38 @@ __device__ __forceinline__ void pileup_tile(const Batch& b, const int32_t* __res
     }
 }
 
+// What a mode's pileup kernel takes beside the plain arguments: nothing, flag[n] beside the batch's per-read
+// columns and the reverse planes, or mapq[n] and the two sum plane sets (all indexed like planes).  A plain
+// handle's kernel so carries no strand or quality argument.
+template <int kMode>
+struct PileupMode {};
+template <>
+struct PileupMode<kModeStrand> {
+    const uint16_t* flag;
+    uint32_t* rev;
+};
+template <>
+struct PileupMode<kModeQuality> {
+    const uint8_t* mapq;
+    uint32_t *bq, *mq;
+};
+
+// One workgroup per tile (kQSub per tile in the quality mode).
+template <int kMode>
 __global__ __launch_bounds__(kThreads) void bases_pileup_kernel(Batch b, const int32_t* __restrict__ span,
                                                                const Tile* __restrict__ tiles,
                                                                const int32_t* __restrict__ order, int32_t max_span,
                                                                int32_t min_baseq, uint32_t* __restrict__ planes,
-                                                               int64_t stride) {
-    pileup_tile<kModePlain>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr, nullptr,
-                            nullptr, nullptr);
-}
-
-// The strand instantiation: flag[n] beside the batch's per-read columns, rev
-// the reverse planes (indexed like planes).
-__global__ __launch_bounds__(kThreads) void bases_pileup_strand_kernel(Batch b, const int32_t* __restrict__ span,
-                                                                      const Tile* __restrict__ tiles,
-                                                                      const int32_t* __restrict__ order,
-                                                                      int32_t max_span, int32_t min_baseq,
-                                                                      uint32_t* __restrict__ planes, int64_t stride,
-                                                                      const uint16_t* __restrict__ flag,
-                                                                      uint32_t* __restrict__ rev) {
-    pileup_tile<kModeStrand>(b, span, tiles, order, max_span, min_baseq, planes, stride, flag, rev, nullptr, nullptr,
-                         nullptr);
-}
-
-// The quality instantiation: mapq[n] beside the batch's per-read columns, bq
-// and mq the two sum plane sets (indexed like planes); kQSub workgroups per
-// tile.
-__global__ __launch_bounds__(kThreads) void bases_pileup_quality_kernel(Batch b, const int32_t* __restrict__ span,
-                                                                       const Tile* __restrict__ tiles,
-                                                                       const int32_t* __restrict__ order,
-                                                                       int32_t max_span, int32_t min_baseq,
-                                                                       uint32_t* __restrict__ planes, int64_t stride,
-                                                                       const uint8_t* __restrict__ mapq,
-                                                                       uint32_t* __restrict__ bq,
-                                                                       uint32_t* __restrict__ mq) {
-    pileup_tile<kModeQuality>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr, mapq, bq,
-                              mq);
+                                                               int64_t stride, PileupMode<kMode> m) {
+    if constexpr (kMode == kModeStrand)
+        pileup_tile<kMode>(b, span, tiles, order, max_span, min_baseq, planes, stride, m.flag, m.rev, nullptr, nullptr,
+                           nullptr);
+    else if constexpr (kMode == kModeQuality)
+        pileup_tile<kMode>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr, m.mapq, m.bq,
+                           m.mq);
+    else
+        pileup_tile<kMode>(b, span, tiles, order, max_span, min_baseq, planes, stride, nullptr, nullptr, nullptr,
+                           nullptr, nullptr);
 }
 
 // depth = A + C + G + T + DEL; the base allele is ref (0..3) where given,
@@ -520,23 +517,10 @@ __device__ __forceinline__ uint32_t site_flags(const uint32_t* __restrict__ plan
     return fm;
 }
 
-// The tile's site count from its threads' flag words.
-__device__ __forceinline__ void sites_count_tile(uint32_t fm, int32_t* __restrict__ counts) {
-    __shared__ int32_t wsum[kWaves];
-    int32_t c = __popc(fm);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t sum = 0;
-        for (int i = 0; i < kWaves; ++i) sum += wsum[i];
-        counts[blockIdx.x] = sum;
-    }
-}
-
 // The tile's sites from its threads' flag words: positions and counts in
-// position order; site_rev (or null): the reverse counts (or the bq sums)
+// position order (mc::tile_offsets' order with a 64-bit running offset of its
+// own: through the helper the three emit kernels held 10 to 16 more VGPRs and
+// the strand one measured slower); site_rev (or null): the reverse counts (or the bq sums)
 // beside them; site_mq (or null): the mq sums.
 __device__ __forceinline__ void sites_emit_tile(uint32_t fm, const Tile& t, const uint32_t* __restrict__ planes,
                                                 const uint32_t* __restrict__ rev, int64_t stride,
@@ -582,24 +566,45 @@ __device__ __forceinline__ void sites_emit_tile(uint32_t fm, const Tile& t, cons
     }
 }
 
-// The plain and the strand kernels of the count and the emit pass: thin, so
-// that a handle that never asks for strand runs kernels without the strand
-// arguments (as bases_pileup_kernel).
+// What a mode's sites kernels take beside the plain arguments: nothing, the
+// reverse planes with min_alt and the sites' reverse counts, or the bq and mq
+// planes with both thresholds and the sites' sums.  The count kernel leaves the
+// output pointers alone.  A plain handle's kernels so carry no strand or
+// quality argument.
+template <int kMode>
+struct SitesMode {};
+template <>
+struct SitesMode<kModeStrand> {
+    const uint32_t* rev;
+    uint32_t min_alt;
+    uint32_t* site_rev;
+};
+template <>
+struct SitesMode<kModeQuality> {
+    const uint32_t *bq, *mq;
+    uint32_t min_bq, min_mq;
+    uint32_t *site_bq, *site_mq;
+};
+
+template <int kMode>
+__device__ __forceinline__ uint32_t mode_site_flags(const uint32_t* __restrict__ planes, int64_t stride,
+                                                    const uint8_t* __restrict__ ref, const Tile& t, const SiteArgs& s,
+                                                    const SitesMode<kMode>& m) {
+    if constexpr (kMode == kModeStrand)
+        return site_flags<kMode>(planes, m.rev, nullptr, stride, ref, t, s, m.min_alt, 0);
+    else if constexpr (kMode == kModeQuality)
+        return site_flags<kMode>(planes, m.bq, m.mq, stride, ref, t, s, m.min_bq, m.min_mq);
+    else
+        return site_flags<kMode>(planes, nullptr, nullptr, stride, ref, t, s, 0, 0);
+}
+
+template <int kMode>
 __global__ __launch_bounds__(kThreads) void sites_count_kernel(const uint32_t* __restrict__ planes, int64_t stride,
                                                               const uint8_t* __restrict__ ref,
                                                               const Tile* __restrict__ tiles, SiteArgs s,
-                                                              int32_t* __restrict__ counts) {
+                                                              SitesMode<kMode> m, int32_t* __restrict__ counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags<kModePlain>(planes, nullptr, nullptr, stride, ref, t, s, 0, 0), counts);
-}
-
-__global__ __launch_bounds__(kThreads) void sites_count_strand_kernel(const uint32_t* __restrict__ planes,
-                                                                     const uint32_t* __restrict__ rev, int64_t stride,
-                                                                     const uint8_t* __restrict__ ref,
-                                                                     const Tile* __restrict__ tiles, SiteArgs s,
-                                                                     uint32_t min_alt, int32_t* __restrict__ counts) {
-    const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags<kModeStrand>(planes, rev, nullptr, stride, ref, t, s, min_alt, 0), counts);
+    mc::tile_count<kWaves>(mode_site_flags<kMode>(planes, stride, ref, t, s, m), counts);
 }
 
 // One workgroup.  base[i] = sum of counts[0, i) for i <= n_tiles, then
@@ -615,57 +620,21 @@ __global__ __launch_bounds__(kScanThreads) void tile_scan_kernel(const int32_t* 
     for (int64_t s = threadIdx.x; s <= S; s += kScanThreads) seg_first[s] = base[seg_tile[s]];
 }
 
+template <int kMode>
 __global__ __launch_bounds__(kThreads) void sites_emit_kernel(const uint32_t* __restrict__ planes, int64_t stride,
                                                              const uint8_t* __restrict__ ref,
                                                              const Tile* __restrict__ tiles, SiteArgs s,
-                                                             const int64_t* __restrict__ base,
+                                                             SitesMode<kMode> m, const int64_t* __restrict__ base,
                                                              int64_t* __restrict__ site_pos,
                                                              uint32_t* __restrict__ site_counts) {
     const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags<kModePlain>(planes, nullptr, nullptr, stride, ref, t, s, 0, 0), t, planes, nullptr,
-                    stride, base, site_pos, site_counts, nullptr);
-}
-
-__global__ __launch_bounds__(kThreads) void sites_emit_strand_kernel(const uint32_t* __restrict__ planes,
-                                                                    const uint32_t* __restrict__ rev, int64_t stride,
-                                                                    const uint8_t* __restrict__ ref,
-                                                                    const Tile* __restrict__ tiles, SiteArgs s,
-                                                                    uint32_t min_alt, const int64_t* __restrict__ base,
-                                                                    int64_t* __restrict__ site_pos,
-                                                                    uint32_t* __restrict__ site_counts,
-                                                                    uint32_t* __restrict__ site_rev) {
-    const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags<kModeStrand>(planes, rev, nullptr, stride, ref, t, s, min_alt, 0), t, planes, rev,
-                    stride, base, site_pos, site_counts, site_rev);
-}
-
-// The quality kernels of the two passes: the five allele planes of the counts,
-// the bq and the mq sums; the emit also writes the sites' sums.
-__global__ __launch_bounds__(kThreads) void sites_count_quality_kernel(const uint32_t* __restrict__ planes,
-                                                                      const uint32_t* __restrict__ bq,
-                                                                      const uint32_t* __restrict__ mq, int64_t stride,
-                                                                      const uint8_t* __restrict__ ref,
-                                                                      const Tile* __restrict__ tiles, SiteArgs s,
-                                                                      uint32_t min_bq, uint32_t min_mq,
-                                                                      int32_t* __restrict__ counts) {
-    const Tile t = tiles[blockIdx.x];
-    sites_count_tile(site_flags<kModeQuality>(planes, bq, mq, stride, ref, t, s, min_bq, min_mq), counts);
-}
-
-__global__ __launch_bounds__(kThreads) void sites_emit_quality_kernel(const uint32_t* __restrict__ planes,
-                                                                     const uint32_t* __restrict__ bq,
-                                                                     const uint32_t* __restrict__ mq, int64_t stride,
-                                                                     const uint8_t* __restrict__ ref,
-                                                                     const Tile* __restrict__ tiles, SiteArgs s,
-                                                                     uint32_t min_bq, uint32_t min_mq,
-                                                                     const int64_t* __restrict__ base,
-                                                                     int64_t* __restrict__ site_pos,
-                                                                     uint32_t* __restrict__ site_counts,
-                                                                     uint32_t* __restrict__ site_bq,
-                                                                     uint32_t* __restrict__ site_mq) {
-    const Tile t = tiles[blockIdx.x];
-    sites_emit_tile(site_flags<kModeQuality>(planes, bq, mq, stride, ref, t, s, min_bq, min_mq), t, planes, bq, stride,
-                    base, site_pos, site_counts, site_bq, mq, site_mq);
+    const uint32_t fm = mode_site_flags<kMode>(planes, stride, ref, t, s, m);
+    if constexpr (kMode == kModeStrand)
+        sites_emit_tile(fm, t, planes, m.rev, stride, base, site_pos, site_counts, m.site_rev);
+    else if constexpr (kMode == kModeQuality)
+        sites_emit_tile(fm, t, planes, m.bq, stride, base, site_pos, site_counts, m.site_bq, m.mq, m.site_mq);
+    else
+        sites_emit_tile(fm, t, planes, nullptr, stride, base, site_pos, site_counts, nullptr);
 }
 
 // ---- consensus (the rule is the header's, "Consensus") ----------------------
@@ -800,31 +769,21 @@ __global__ __launch_bounds__(kThreads) void cons_emit_kernel(const uint8_t* __re
                                                             const Tile* __restrict__ tiles,
                                                             const int64_t* __restrict__ base,
                                                             uint8_t* __restrict__ compact) {
-    __shared__ int32_t wcnt[kRounds][kWaves];
     const Tile t = tiles[blockIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t letter[kRounds];
-    int32_t rank[kRounds];                                  // kept letters of this round in lower lanes of the wave
+    uint32_t fm = 0;                                        // bit r: the letter of round r is kept
 #pragma unroll
     for (int r = 0; r < kRounds; ++r) {
         const int k = r * kThreads + (int)threadIdx.x;
         letter[r] = k < t.n ? (uint32_t)aligned[t.out + k] : (uint32_t)'-';
-        const unsigned long long m = __ballot(letter[r] != (uint32_t)'-');
-        rank[r] = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-        if (lane == 0) wcnt[r][wave] = __popcll(m);
+        fm |= (uint32_t)(letter[r] != (uint32_t)'-') << r;
     }
-    __syncthreads();
-    int64_t run = base[blockIdx.x];                         // positions ascend with (round, wave, lane)
+    int32_t rank[kRounds];                                  // positions ascend with (round, wave, lane)
+    mc::tile_offsets<kWaves>(fm, rank);
+    const int64_t first = base[blockIdx.x];
 #pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        int64_t mine = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            if (w == wave) mine = run;
-            run += wcnt[r][w];
-        }
-        if (letter[r] != (uint32_t)'-') compact[mine + rank[r]] = (uint8_t)letter[r];
-    }
+    for (int r = 0; r < kRounds; ++r)
+        if ((fm >> r) & 1) compact[first + rank[r]] = (uint8_t)letter[r];
 }
 
 #include "bases_ins.h"   // the insertion stage's kernels
@@ -849,20 +808,29 @@ struct InsTable {
     bool valid = false;
 };
 
+// The handle's timing events: a span of a *_timing call lies between two of
+// them (the consensus' call ends where its scan begins, the diversity's zero
+// pass where its tile pass begins).
+enum {
+    kEvPrepass, kEvPrepassEnd, kEvPileup, kEvPileupEnd, kEvSites, kEvSitesEnd,
+    kEvConsCall, kEvConsScan, kEvConsScanEnd, kEvConsEmit, kEvConsEmitEnd,
+    kEvDivZero, kEvDivTile, kEvDivEnd,
+    kEvInsExtract, kEvInsExtractEnd, kEvInsGroup, kEvInsGroupEnd, kEvInsCons, kEvInsConsEnd,
+    kEvents
+};
+
 }  // namespace
 
-struct mc_bases {
-    int device = 0;
+// pin: [0] lowest bad read, [1] max span (int32), [2] site total, [3] consensus total, [4] insertion totals,
+// [7] the diversity's bad index
+struct mc_bases : mc::StageHandle<kEvents, 8> {
     int32_t n_ref = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned long long* pin = nullptr;   // [0] lowest bad read, [1] max span (int32), [2] site total, [3] consensus
-                                         // total, [4] insertion totals (8 words in all)
     // segments and planes (mc_bases_begin)
     bool begun = false;
     int32_t min_baseq = 0;
     int64_t S = 0, N = 0, stride = 4, n_tiles = 0;
     std::vector<int64_t> seg_off;
+    std::vector<int64_t> tile_out;       // the tiles' first plane indices, on the host (diversity, mc_bases_ins_set)
     Buf<Tile> tiles;
     Buf<int32_t> order;                  // the tiles sorted by (tid, rel)
     std::vector<std::pair<int32_t, int64_t>> tile_key;   // (tid, rel) of order[i], on the host
@@ -877,10 +845,10 @@ struct mc_bases {
     bool have_last = false;
     int32_t last_tid = 0, last_pos = 0;
     int64_t n_reads = 0;
+    Buf<uint8_t> ref;                    // the reference plane of the call in flight (upload_ref)
     // sites
     bool have_sites = false;
     int64_t n_sites = 0;
-    Buf<uint8_t> ref;
     Buf<int32_t> counts;
     Buf<int64_t> base, site_first, site_pos;
     Buf<uint32_t> site_counts;
@@ -888,8 +856,7 @@ struct mc_bases {
     // consensus: buffers of its own, so sites and a consensus live side by side
     bool have_cons = false;
     int64_t n_cons = 0;                  // compact letters in all
-    hipEvent_t cev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    Buf<uint8_t> cons_ref, cons_aligned, cons_compact;
+    Buf<uint8_t> cons_aligned, cons_compact;
     Buf<int32_t> cons_cols;              // [8][T]
     Buf<int64_t> cons_pre, cons_first, cons_rows;   // [8][T + 1], [S + 1], [S][8]
     float ms_cons_call = 0, ms_cons_scan = 0, ms_cons_emit = 0;
@@ -897,8 +864,6 @@ struct mc_bases {
     bool have_div = false;
     int64_t n_div = 0;                   // windows in all
     std::vector<int64_t> div_first;      // [S + 1]
-    hipEvent_t dev[3] = {nullptr, nullptr, nullptr};
-    Buf<uint8_t> div_ref;
     Buf<DivTile> div_tiles;              // [T]
     Buf<int64_t> div_rows;               // [n_div][8]
     Buf<unsigned long long> div_bad;     // the lowest covered plane index with 2^26 bases or more (pin[7] on the host)
@@ -909,7 +874,6 @@ struct mc_bases {
     int64_t n_events = 0;
     InsEvent* events = nullptr;          // grows with its contents kept
     size_t events_cap = 0;
-    std::vector<int64_t> tile_out;       // the tiles' first plane indices, on the host (mc_bases_ins_set)
     Buf<int32_t> ins_counts, tile_total, ins_cursor;
     Buf<int64_t> ins_base, ins_bbase;
     bool sorted_valid = false, have_weight = false;
@@ -920,7 +884,6 @@ struct mc_bases {
     Buf<int32_t> cons_ins_cols;          // [2][T]: bases inserted, insertions called
     Buf<int64_t> cons_ins_pre, cons_ins_first, cons_ins_rows;   // [2][T + 1], [2][S + 1], [S][2]
     bool have_cons_ins = false;
-    hipEvent_t iev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms_ins_extract = 0, ms_ins_group = 0, ms_ins_cons = 0;
     // strand (opt-in, mc_bases_track_strand): the reverse-strand reads' planes beside the totals
     bool strand_next = false, strand = false;
@@ -935,17 +898,7 @@ struct mc_bases {
     bool have_sites_q = false;           // the sites are mc_bases_sites_quality's: site_bq and site_mq are filled
     Buf<uint32_t> site_bq, site_mq;
     ~mc_bases() {
-        for (auto& e : iev)
-            if (e) (void)hipEventDestroy(e);
         if (events) (void)hipFree(events);
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : cev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : dev)
-            if (e) (void)hipEventDestroy(e);
-        if (pin) (void)hipHostFree(pin);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -969,11 +922,13 @@ int copy_planes(const mc_bases* h, uint32_t* dst, int64_t dst_stride, const uint
     return MC_OK;
 }
 
-// The last element of a scan (8 bytes at d_src) through pin[slot], behind what is on the stream.
-int read_total(mc_bases* h, const int64_t* d_src, int slot, int64_t* total) {
-    HIP_TRY(hipMemcpyAsync(h->pin + slot, d_src, 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    std::memcpy(total, h->pin + slot, 8);
+// The caller's reference plane (N codes, or null) in device memory for the call in flight: *d_ref, or null.
+int upload_ref(mc_bases* h, const uint8_t* ref, const uint8_t** d_ref) {
+    *d_ref = nullptr;
+    if (!ref || !h->N) return MC_OK;
+    HIP_TRY(h->ref.reserve((size_t)h->N));
+    HIP_TRY(hipMemcpyAsync(h->ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, h->stream));
+    *d_ref = h->ref.p;
     return MC_OK;
 }
 
@@ -997,36 +952,18 @@ extern "C" int mc_bases_create(int device, int32_t n_ref, mc_bases** out) {
     MC_REQUIRE(out, MC_E_INVALID, "null argument");
     *out = nullptr;
     MC_REQUIRE(n_ref >= 0, MC_E_INVALID, "n_ref %d is negative", n_ref);
-    int n_dev = 0;
-    HIP_TRY(hipGetDeviceCount(&n_dev));
-    MC_REQUIRE(device >= 0 && device < n_dev, MC_E_HIP, "no HIP device %d (%d present)", device, n_dev);
-    HIP_TRY(hipSetDevice(device));
-    mc_bases* h = new mc_bases();
-    h->device = device;
-    h->n_ref = n_ref;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipHostMalloc((void**)&h->pin, 8 * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess &&
-              h->flags.reserve(2) == hipSuccess;
-    for (auto& e : h->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    for (auto& e : h->cev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    for (auto& e : h->dev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    for (auto& e : h->iev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    if (!ok) {
-        delete h;
+    if (int rc = mc::stage_create(device, out)) return rc;
+    (*out)->n_ref = n_ref;
+    if ((*out)->flags.reserve(2) != hipSuccess) {
+        delete *out;
+        *out = nullptr;
         mc::set_error("HIP stream / event creation failed");
         return MC_E_HIP;
     }
-    *out = h;
     return MC_OK;
 }
 
-extern "C" int mc_bases_destroy(mc_bases* h) {
-    if (h) {
-        (void)hipSetDevice(h->device);
-        delete h;
-    }
-    return MC_OK;
-}
+extern "C" int mc_bases_destroy(mc_bases* h) { return mc::stage_destroy(h); }
 
 extern "C" int mc_bases_dims(int32_t* tile) {
     MC_REQUIRE(tile, MC_E_INVALID, "null argument");
@@ -1058,32 +995,28 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     std::vector<int64_t> seg_tile((size_t)S + 1), seg_off((size_t)S + 1);
     int64_t N = 0;
     for (int64_t s = 0; s < S; ++s) {
-        MC_REQUIRE(tid[s] >= 0 && tid[s] < h->n_ref, MC_E_INVALID, "segment %lld: tid %d out of range",
-                   (long long)s, tid[s]);
-        MC_REQUIRE(start[s] >= 0 && end[s] >= start[s] && end[s] <= kMaxPos, MC_E_INVALID,
-                   "segment %lld: bad range [%lld, %lld)", (long long)s, (long long)start[s], (long long)end[s]);
+        if (tid[s] < 0 || tid[s] >= h->n_ref) return mc::bad_segment_tid(s, tid[s]);
+        if (int rc = mc::check_segment_range(s, start, end)) return rc;
         seg_tile[s] = (int64_t)tiles.size();
         seg_off[s] = N;
-        for (int64_t a = start[s]; a < end[s];) {
-            Tile t;
-            t.out = N;
-            t.rel = a;
-            t.lead = (int32_t)(N & 3);
-            t.n = (int32_t)std::min<int64_t>(kTile - t.lead, end[s] - a);
-            t.tid = tid[s];
-            t.seg = (int32_t)std::min<int64_t>(s, INT32_MAX);
-            tiles.push_back(t);
-            a += t.n;
-            N += t.n;
-            MC_REQUIRE(tiles.size() < (size_t)INT32_MAX, MC_E_RANGE, "more than 2^31 tiles of %d positions",
-                       kTile);
-        }
+        const int rc = mc::cut_tiles(
+            tiles, kTile, start[s], end[s], 1, [&](int64_t) { return (int)(N & 3); },
+            [&](int64_t a, int64_t n) {
+                Tile t;
+                t.out = N;
+                t.rel = a;
+                t.lead = (int32_t)(N & 3);
+                t.n = (int32_t)n;
+                t.tid = tid[s];
+                t.seg = (int32_t)std::min<int64_t>(s, INT32_MAX);
+                N += n;
+                return t;
+            });
+        if (rc) return rc;
     }
     const int64_t T = (int64_t)tiles.size();
-    seg_tile[S] = T;
     seg_off[S] = N;
-    for (int64_t s = S - 1; s >= 0; --s)          // an empty segment: the next non-empty one's first tile
-        if (end[s] == start[s]) seg_tile[s] = seg_tile[s + 1];
+    mc::close_seg_tile(seg_tile, T, start, end);
     const int64_t stride = std::max<int64_t>(4, (N + 3) & ~int64_t(3));   // every plane 16-byte aligned
     // the tiles in (tid, rel) order: a batch launches only the range of them its reads can reach
     std::vector<int32_t> order((size_t)T);
@@ -1127,11 +1060,8 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->sorted_valid = h->have_weight = false;
     h->tab_user.valid = h->tab_cons.valid = false;
     h->ms_ins_extract = h->ms_ins_group = h->ms_ins_cons = 0;
-    h->tile_out.clear();
-    if (h->tracking) {
-        h->tile_out.resize((size_t)T);
-        for (int64_t i = 0; i < T; ++i) h->tile_out[(size_t)i] = tiles[(size_t)i].out;
-    }
+    h->tile_out.resize((size_t)T);
+    for (int64_t i = 0; i < T; ++i) h->tile_out[(size_t)i] = tiles[(size_t)i].out;
     h->S = S;
     h->N = N;
     h->stride = stride;
@@ -1210,7 +1140,7 @@ int ins_extract(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t 
     invalidate_ins(h);
     HIP_TRY(h->ins_counts.reserve((size_t)nt));
     HIP_TRY(h->ins_base.reserve((size_t)nt + 1));
-    HIP_TRY(hipEventRecord(h->iev[0], st));
+    if (int rc = h->mark(kEvInsExtract)) return rc;
     hipLaunchKernelGGL(ins_extract_kernel<false>, dim3((unsigned)nt), dim3(kThreads), 0, st, b, h->span.p, h->tiles.p,
                        h->order.p + first, max_span, h->ins_counts.p, (const int64_t*)nullptr, (InsEvent*)nullptr,
                        (int64_t)0, (int32_t*)nullptr);
@@ -1219,7 +1149,7 @@ int ins_extract(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t 
                        (const int64_t*)nullptr, (int64_t)-1, (int64_t*)nullptr);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
-    if (int rc = read_total(h, h->ins_base.p + nt, 4, &total)) return rc;
+    if (int rc = h->read_total(h->ins_base.p + nt, 4, &total)) return rc;
     MC_REQUIRE(total >= 0, MC_E_STATE, "insertion event count %lld out of range", (long long)total);
     MC_REQUIRE(h->n_events + total <= kMaxEvents, MC_E_RANGE, "more than 2^31 - 1 insertion events");
     if (total) {
@@ -1230,10 +1160,10 @@ int ins_extract(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t 
                            h->events + h->n_events, total, h->tile_total.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->iev[1], st));
+    if (int rc = h->mark(kEvInsExtractEnd)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, h->iev[0], h->iev[1]));
+    if (int rc = h->elapsed(kEvInsExtract, kEvInsExtractEnd, &ms)) return rc;
     h->ms_ins_extract += ms;
     h->n_events += total;
     h->sorted_valid = false;
@@ -1286,7 +1216,7 @@ int ins_encode(mc_bases* h, const SiteArgs& sa, InsTable& tab) {
                        h->seg_tile.p, S, tab.first.p);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
-    if (int rc = read_total(h, tab.rowbase.p + T, 4, &total)) return rc;
+    if (int rc = h->read_total(tab.rowbase.p + T, 4, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= h->n_events, MC_E_STATE, "insertion row count %lld out of range",
                (long long)total);
     HIP_TRY(tab.i.reserve((size_t)total));
@@ -1320,22 +1250,53 @@ __global__ void bases_ends_kernel(Batch b, int32_t* __restrict__ ends) {
     }
 }
 
+// f(std::integral_constant<int, mode>()): the one place where the host picks a mode's kernels.
+template <typename F>
+void for_mode(int mode, F f) {
+    if (mode == kModeQuality)
+        f(std::integral_constant<int, kModeQuality>());
+    else if (mode == kModeStrand)
+        f(std::integral_constant<int, kModeStrand>());
+    else
+        f(std::integral_constant<int, kModePlain>());
+}
+
+PileupMode<kModePlain> pileup_mode(const mc_bases*, const uint16_t*, const uint8_t*,
+                                   std::integral_constant<int, kModePlain>) {
+    return {};
+}
+PileupMode<kModeStrand> pileup_mode(const mc_bases* h, const uint16_t* flag, const uint8_t*,
+                                    std::integral_constant<int, kModeStrand>) {
+    return {flag, h->rev.p};
+}
+PileupMode<kModeQuality> pileup_mode(const mc_bases* h, const uint16_t*, const uint8_t* mapq,
+                                     std::integral_constant<int, kModeQuality>) {
+    return {mapq, h->bq.p, h->mq.p};
+}
+
+SitesMode<kModePlain> sites_mode(const mc_bases*, uint32_t, uint32_t, std::integral_constant<int, kModePlain>) {
+    return {};
+}
+SitesMode<kModeStrand> sites_mode(const mc_bases* h, uint32_t min_alt, uint32_t,
+                                  std::integral_constant<int, kModeStrand>) {
+    return {h->rev.p, min_alt, h->site_rev.p};
+}
+SitesMode<kModeQuality> sites_mode(const mc_bases* h, uint32_t min_bq, uint32_t min_mq,
+                                   std::integral_constant<int, kModeQuality>) {
+    return {h->bq.p, h->mq.p, min_bq, min_mq, h->site_bq.p, h->site_mq.p};
+}
+
 // The pileup launch of a batch over tiles [first, first + nt) of the sorted
 // order; flag: the reads' flags in device memory on a handle that tracks
 // strand; mapq: their MAPQ bytes there on one that tracks quality.
 void launch_pileup(mc_bases* h, const Batch& b, int64_t first, int64_t nt, int32_t max_span, const uint16_t* flag,
                    const uint8_t* mapq) {
-    if (h->quality)
-        hipLaunchKernelGGL(bases_pileup_quality_kernel, dim3((unsigned)(nt * kQSub)), dim3(kThreads), 0, h->stream, b,
-                           h->span.p, h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride,
-                           mapq, h->bq.p, h->mq.p);
-    else if (h->strand)
-        hipLaunchKernelGGL(bases_pileup_strand_kernel, dim3((unsigned)nt), dim3(kThreads), 0, h->stream, b, h->span.p,
-                           h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride, flag,
-                           h->rev.p);
-    else
-        hipLaunchKernelGGL(bases_pileup_kernel, dim3((unsigned)nt), dim3(kThreads), 0, h->stream, b, h->span.p,
-                           h->tiles.p, h->order.p + first, max_span, h->min_baseq, h->planes.p, h->stride);
+    for_mode(h->quality ? kModeQuality : h->strand ? kModeStrand : kModePlain, [&](auto mode) {
+        constexpr int kMode = decltype(mode)::value;
+        hipLaunchKernelGGL(bases_pileup_kernel<kMode>, dim3((unsigned)(nt * (kMode == kModeQuality ? kQSub : 1))),
+                           dim3(kThreads), 0, h->stream, b, h->span.p, h->tiles.p, h->order.p + first, max_span,
+                           h->min_baseq, h->planes.p, h->stride, pileup_mode(h, flag, mapq, mode));
+    });
 }
 
 // The per-read column a batch entry point takes beside the nine arrays: none,
@@ -1399,11 +1360,11 @@ int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const ui
     HIP_TRY(hipMemcpyAsync(h->flags.p, h->pin, 16, hipMemcpyHostToDevice, st));
     const int64_t groups = (b.n + kThreads - 1) / kThreads;
     MC_REQUIRE(groups < (int64_t)INT32_MAX, MC_E_RANGE, "more than 2^39 reads in one batch");
-    HIP_TRY(hipEventRecord(h->ev[0], st));
+    if (int rc = h->mark(kEvPrepass)) return rc;
     hipLaunchKernelGGL(bases_prepass_kernel, dim3((unsigned)groups), dim3(kThreads), 0, st, b, h->n_ref, h->span.p,
                        h->flags.p, reinterpret_cast<int32_t*>(h->flags.p + 1));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->ev[1], st));
+    if (int rc = h->mark(kEvPrepassEnd)) return rc;
     if (!host_ends) {
         hipLaunchKernelGGL(bases_ends_kernel, dim3(1), dim3(64), 0, st, b, reinterpret_cast<int32_t*>(h->flags.p + 2));
         HIP_TRY(hipGetLastError());
@@ -1424,7 +1385,7 @@ int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const ui
     int32_t max_span = 0;
     std::memcpy(&max_span, &h->pin[1], 4);
     MC_REQUIRE(max_span >= 0, MC_E_STATE, "maximum span %d out of range", max_span);
-    HIP_TRY(hipEventRecord(h->ev[2], st));
+    if (int rc = h->mark(kEvPileup)) return rc;
     // A tile the batch can reach starts after (first read's pos - kTile) and before (last read's pos +
     // max span), in (tid, rel) order: only that range of the sorted tiles is launched.
     const auto t_lo = std::lower_bound(h->tile_key.begin(), h->tile_key.end(),
@@ -1435,15 +1396,15 @@ int finish_batch(mc_bases* h, const Batch& b, const int32_t* host_ends, const ui
         launch_pileup(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span, flag, mapq);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->ev[3], st));
+    if (int rc = h->mark(kEvPileupEnd)) return rc;
     if (h->tracking && max_span > 0 && t_lo < t_hi) {
         const int rc = ins_extract(h, b, t_lo - h->tile_key.begin(), t_hi - t_lo, max_span);
         if (rc != MC_OK) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));            // the caller's arrays and the handle's batch buffers are free again
     float a = 0, c = 0;
-    HIP_TRY(hipEventElapsedTime(&a, h->ev[0], h->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&c, h->ev[2], h->ev[3]));
+    if (int rc = h->elapsed(kEvPrepass, kEvPrepassEnd, &a)) return rc;
+    if (int rc = h->elapsed(kEvPileup, kEvPileupEnd, &c)) return rc;
     h->ms_prepass += a;
     h->ms_pileup += c;
     h->have_last = true;
@@ -1656,29 +1617,21 @@ int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, in
     HIP_TRY(h->site_first.reserve((size_t)S + 1));
     hipStream_t st = h->stream;
     const uint8_t* d_ref = nullptr;
-    if (ref && h->N) {
-        HIP_TRY(h->ref.reserve((size_t)h->N));
-        HIP_TRY(hipMemcpyAsync(h->ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, st));
-        d_ref = h->ref.p;
-    }
-    HIP_TRY(hipEventRecord(h->ev[4], st));
+    if (int rc = upload_ref(h, ref, &d_ref)) return rc;
+    if (int rc = h->mark(kEvSites)) return rc;
     if (T) {
-        if (quality)
-            hipLaunchKernelGGL(sites_count_quality_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
-                               h->bq.p, h->mq.p, h->stride, d_ref, h->tiles.p, sa, k_alt, k_mq, h->counts.p);
-        else if (strand)
-            hipLaunchKernelGGL(sites_count_strand_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
-                               h->rev.p, h->stride, d_ref, h->tiles.p, sa, k_alt, h->counts.p);
-        else
-            hipLaunchKernelGGL(sites_count_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride,
-                               d_ref, h->tiles.p, sa, h->counts.p);
+        for_mode(mode, [&](auto m) {
+            hipLaunchKernelGGL(sites_count_kernel<decltype(m)::value>, dim3((unsigned)T), dim3(kThreads), 0, st,
+                               h->planes.p, h->stride, d_ref, h->tiles.p, sa, sites_mode(h, k_alt, k_mq, m),
+                               h->counts.p);
+        });
         HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->counts.p, T, h->base.p,
                        h->seg_tile.p, S, h->site_first.p);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
-    if (int rc = read_total(h, h->base.p + T, 2, &total)) return rc;
+    if (int rc = h->read_total(h->base.p + T, 2, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "site count %lld out of range", (long long)total);
     HIP_TRY(h->site_pos.reserve((size_t)total));
     HIP_TRY(h->site_counts.reserve((size_t)total * kPlanes));
@@ -1688,22 +1641,16 @@ int sites(mc_bases* h, int64_t min_depth, int64_t min_count, int64_t min_ppm, in
         HIP_TRY(h->site_mq.reserve((size_t)total * kPlanes));
     }
     if (T) {
-        if (quality)
-            hipLaunchKernelGGL(sites_emit_quality_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
-                               h->bq.p, h->mq.p, h->stride, d_ref, h->tiles.p, sa, k_alt, k_mq, h->base.p,
-                               h->site_pos.p, h->site_counts.p, h->site_bq.p, h->site_mq.p);
-        else if (strand)
-            hipLaunchKernelGGL(sites_emit_strand_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p,
-                               h->rev.p, h->stride, d_ref, h->tiles.p, sa, k_alt, h->base.p, h->site_pos.p,
-                               h->site_counts.p, h->site_rev.p);
-        else
-            hipLaunchKernelGGL(sites_emit_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride,
-                               d_ref, h->tiles.p, sa, h->base.p, h->site_pos.p, h->site_counts.p);
+        for_mode(mode, [&](auto m) {      // (after the reserves: the mode's output pointers are final)
+            hipLaunchKernelGGL(sites_emit_kernel<decltype(m)::value>, dim3((unsigned)T), dim3(kThreads), 0, st,
+                               h->planes.p, h->stride, d_ref, h->tiles.p, sa, sites_mode(h, k_alt, k_mq, m),
+                               h->base.p, h->site_pos.p, h->site_counts.p);
+        });
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->ev[5], st));
+    if (int rc = h->mark(kEvSitesEnd)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&h->ms_sites, h->ev[4], h->ev[5]));   // (the 8-byte read-back included)
+    if (int rc = h->elapsed(kEvSites, kEvSitesEnd, &h->ms_sites)) return rc;   // (the 8-byte read-back included)
     h->n_sites = total;
     h->have_sites = true;
     h->have_sites_rev = strand;
@@ -1954,30 +1901,26 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
     HIP_TRY(h->cons_rows.reserve((size_t)(S * kConsCols)));
     hipStream_t st = h->stream;
     const uint8_t* d_ref = nullptr;
-    if (ref && h->N) {
-        HIP_TRY(h->cons_ref.reserve((size_t)h->N));
-        HIP_TRY(hipMemcpyAsync(h->cons_ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, st));
-        d_ref = h->cons_ref.p;
-    }
-    HIP_TRY(hipEventRecord(h->cev[0], st));
+    if (int rc = upload_ref(h, ref, &d_ref)) return rc;
+    if (int rc = h->mark(kEvConsCall)) return rc;
     if (T) {
         hipLaunchKernelGGL(cons_call_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
                            h->tiles.p, T, ca, h->cons_aligned.p, h->cons_cols.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->cev[1], st));
+    if (int rc = h->mark(kEvConsScan)) return rc;
     hipLaunchKernelGGL(cons_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, h->cons_cols.p, T, h->cons_pre.p,
                        h->seg_tile.p, S, h->cons_first.p, h->cons_rows.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->cev[2], st));
+    if (int rc = h->mark(kEvConsScanEnd)) return rc;
     int64_t total = 0;
-    if (int rc = read_total(h, h->cons_pre.p + 7 * (T + 1) + T, 3, &total)) return rc;
+    if (int rc = h->read_total(h->cons_pre.p + 7 * (T + 1) + T, 3, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= h->N, MC_E_STATE, "consensus length %lld out of range", (long long)total);
     int64_t inserted = 0;
     if (with_ins) {
         // the rows that qualify at a position that is not LOW, the top allele of each position, the two
         // per-tile columns (bases inserted, insertions called) and their prefixes
-        HIP_TRY(hipEventRecord(h->iev[4], st));
+        if (int rc = h->mark(kEvInsCons)) return rc;
         int rc = ins_sort(h);
         if (rc != MC_OK) return rc;
         rc = ins_encode(h, SiteArgs{ca.min_depth, ca.min_count, ca.call_ppm}, h->tab_cons);
@@ -2004,15 +1947,15 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
                            h->cons_ins_first.p, h->cons_ins_first.p + (S + 1), h->cons_first.p, h->cons_rows.p,
                            h->cons_ins_rows.p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(h->iev[5], st));
-        rc = read_total(h, h->cons_ins_pre.p + T, 4, &inserted);
+        if (int rc = h->mark(kEvInsConsEnd)) return rc;
+        rc = h->read_total(h->cons_ins_pre.p + T, 4, &inserted);
         if (rc != MC_OK) return rc;
         MC_REQUIRE(inserted >= 0 && inserted <= kMaxInsLen * tb.n, MC_E_STATE, "inserted bases %lld out of range",
                    (long long)inserted);
-        HIP_TRY(hipEventElapsedTime(&h->ms_ins_cons, h->iev[4], h->iev[5]));
+        if (int rc = h->elapsed(kEvInsCons, kEvInsConsEnd, &h->ms_ins_cons)) return rc;
     }
     HIP_TRY(h->cons_compact.reserve((size_t)(total + inserted)));
-    HIP_TRY(hipEventRecord(h->cev[3], st));
+    if (int rc = h->mark(kEvConsEmit)) return rc;
     if (T) {
         if (with_ins) {
             const InsTable& tb = h->tab_cons;
@@ -2025,11 +1968,11 @@ extern "C" int mc_bases_consensus(mc_bases* h, int64_t min_depth, int64_t min_co
         }
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->cev[4], st));
+    if (int rc = h->mark(kEvConsEmitEnd)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&h->ms_cons_call, h->cev[0], h->cev[1]));
-    HIP_TRY(hipEventElapsedTime(&h->ms_cons_scan, h->cev[1], h->cev[2]));
-    HIP_TRY(hipEventElapsedTime(&h->ms_cons_emit, h->cev[3], h->cev[4]));
+    if (int rc = h->elapsed(kEvConsCall, kEvConsScan, &h->ms_cons_call)) return rc;
+    if (int rc = h->elapsed(kEvConsScan, kEvConsScanEnd, &h->ms_cons_scan)) return rc;
+    if (int rc = h->elapsed(kEvConsEmit, kEvConsEmitEnd, &h->ms_cons_emit)) return rc;
     h->n_cons = total + inserted;
     h->have_cons = true;
     h->have_cons_ins = with_ins;
@@ -2102,27 +2045,25 @@ extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth
                (long long)window, MC_DIV_MIN_WINDOW);
     h->have_div = false;
     const int64_t T = h->n_tiles, S = h->S;
-    // the windows (arithmetic) and, per tile, its first window and where in it the tile starts: the tile
-    // table again, as mc_bases_begin cut it from the segments' lengths
+    // the windows (arithmetic) and, per tile of mc_bases_begin's cut, its first window and where in it the
+    // tile starts: tile_out against seg_off is the tile's offset inside its segment
     std::vector<int64_t> first((size_t)S + 1);
-    std::vector<DivTile> dt;
-    dt.reserve((size_t)T);
     int64_t nw = 0;
     for (int64_t s = 0; s < S; ++s) {
         first[(size_t)s] = nw;
-        const int64_t a = h->seg_off[(size_t)s], len = h->seg_off[(size_t)s + 1] - a;
-        for (int64_t p = 0; p < len;) {
-            const int64_t n = std::min<int64_t>(kTile - ((a + p) & 3), len - p);
-            dt.push_back(window ? DivTile{nw + p / window, p % window} : DivTile{nw, p});
-            p += n;
-        }
+        const int64_t len = h->seg_off[(size_t)s + 1] - h->seg_off[(size_t)s];
         nw += window ? (len + window - 1) / window : (len > 0);
         MC_REQUIRE(nw <= (int64_t(1) << 31), MC_E_RANGE, "more than 2^31 windows of %lld positions",
                    (long long)window);
     }
     first[(size_t)S] = nw;
-    MC_REQUIRE((int64_t)dt.size() == T, MC_E_STATE, "tile table of %lld entries, %lld expected", (long long)dt.size(),
-               (long long)T);
+    std::vector<DivTile> dt((size_t)T);
+    for (int64_t i = 0, s = 0; i < T; ++i) {
+        const int64_t out = h->tile_out[(size_t)i];
+        while (h->seg_off[(size_t)s + 1] <= out) ++s;       // tiles and segments ascend together; out < N
+        const int64_t p = out - h->seg_off[(size_t)s];
+        dt[(size_t)i] = window ? DivTile{first[(size_t)s] + p / window, p % window} : DivTile{first[(size_t)s], p};
+    }
     const DivArgs da{(unsigned long long)std::max<int64_t>(min_depth, 2),
                      (unsigned long long)std::max<int64_t>(min_count, 1), (unsigned long long)min_ppm,
                      window ? window : 2 * kMaxPos};
@@ -2132,35 +2073,31 @@ extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth
     HIP_TRY(h->div_bad.reserve(1));
     hipStream_t st = h->stream;
     const uint8_t* d_ref = nullptr;
-    if (ref && h->N) {
-        HIP_TRY(h->div_ref.reserve((size_t)h->N));
-        HIP_TRY(hipMemcpyAsync(h->div_ref.p, ref, (size_t)h->N, hipMemcpyHostToDevice, st));
-        d_ref = h->div_ref.p;
-    }
+    if (int rc = upload_ref(h, ref, &d_ref)) return rc;
     h->pin[7] = kNoBad;
     HIP_TRY(hipMemcpyAsync(h->div_bad.p, h->pin + 7, 8, hipMemcpyHostToDevice, st));
     if (T) HIP_TRY(hipMemcpyAsync(h->div_tiles.p, dt.data(), (size_t)T * sizeof(DivTile), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(h->dev[0], st));
+    if (int rc = h->mark(kEvDivZero)) return rc;
     if (T) {
         hipLaunchKernelGGL(div_zero_kernel, dim3((unsigned)((T * 16 + 255) / 256)), dim3(256), 0, st, h->tiles.p,
                            h->div_tiles.p, T, da.window, h->div_rows.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->dev[1], st));
+    if (int rc = h->mark(kEvDivTile)) return rc;
     if (T) {
         hipLaunchKernelGGL(div_tile_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
                            h->tiles.p, h->div_tiles.p, da, h->div_rows.p, h->div_bad.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(h->dev[2], st));
+    if (int rc = h->mark(kEvDivEnd)) return rc;
     HIP_TRY(hipMemcpyAsync(h->pin + 7, h->div_bad.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));            // (dt is released)
     const unsigned long long bad = h->pin[7];
     MC_REQUIRE(bad == kNoBad, MC_E_RANGE,
                "plane index %llu: A + C + G + T of a covered position is 2^26 or more (pi_fix is exact below that)",
                bad);
-    HIP_TRY(hipEventElapsedTime(&h->ms_div_zero, h->dev[0], h->dev[1]));
-    HIP_TRY(hipEventElapsedTime(&h->ms_div_tile, h->dev[1], h->dev[2]));
+    if (int rc = h->elapsed(kEvDivZero, kEvDivTile, &h->ms_div_zero)) return rc;
+    if (int rc = h->elapsed(kEvDivTile, kEvDivEnd, &h->ms_div_tile)) return rc;
     h->div_first = std::move(first);
     h->n_div = nw;
     h->have_div = true;
@@ -2224,14 +2161,14 @@ extern "C" int mc_bases_insertions(mc_bases* h, int64_t min_depth, int64_t min_c
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     const SiteArgs sa{(unsigned long long)min_depth, (unsigned long long)min_count, (unsigned long long)min_ppm};
-    HIP_TRY(hipEventRecord(h->iev[2], st));
+    if (int rc = h->mark(kEvInsGroup)) return rc;
     int rc = ins_sort(h);
     if (rc != MC_OK) return rc;
     rc = ins_encode(h, sa, h->tab_user);
     if (rc != MC_OK) return rc;
-    HIP_TRY(hipEventRecord(h->iev[3], st));
+    if (int rc = h->mark(kEvInsGroupEnd)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&h->ms_ins_group, h->iev[2], h->iev[3]));   // (the 8-byte read-back included)
+    if (int rc = h->elapsed(kEvInsGroup, kEvInsGroupEnd, &h->ms_ins_group)) return rc;   // (the 8-byte read-back included)
     *n_rows = h->tab_user.n;
     return MC_OK;
 }

@@ -50,7 +50,6 @@ constexpr int kRounds = 8;                          // int4 loads per lane
 constexpr int kTile = kThreads * 4 * kRounds;       // 8192 positions
 constexpr int kWavePos = kTile / kWaves;            // 2048
 constexpr int kMaxEdges = 16;
-constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_set_contigs' length bound
 
 struct Tile {
     int64_t first;     // depth-vector index of the tile's first position
@@ -132,21 +131,10 @@ template <bool Q>
 __global__ __launch_bounds__(kThreads) void runs_count_kernel(const int32_t* __restrict__ d,
                                                              const Tile* __restrict__ tiles, Edges E,
                                                              int32_t* __restrict__ counts) {
-    __shared__ int32_t wsum[kWaves];
     const Tile t = tiles[blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int32_t qv[kRounds][4];
-    const uint32_t fm = tile_flags<Q>(d, t, E, lead_of(d, t), wave, lane, qv);
-    int32_t c = __popc(fm);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
-    if (lane == 0) wsum[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int32_t s = 0;
-        for (int i = 0; i < kWaves; ++i) s += wsum[i];
-        counts[blockIdx.x] = s;
-    }
+    mc::tile_count<kWaves>(tile_flags<Q>(d, t, E, lead_of(d, t), wave, lane, qv), counts);
 }
 
 // One workgroup.  base[i] = sum of counts[0, i) for i <= n_tiles, then
@@ -208,11 +196,12 @@ __global__ __launch_bounds__(kThreads) void runs_emit_kernel(const int32_t* __re
 
 }  // namespace
 
-struct mc_runs {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int64_t* pin_total = nullptr;      // the grand total, read between B and C
+namespace {
+enum { kEvCount, kEvScan, kEvScanEnd, kEvEmit, kEvEmitEnd, kEvents };   // the count pass ends where the scan begins
+}
+
+// pin[0]: the grand total, read between B and C
+struct mc_runs : mc::StageHandle<kEvents, 1> {
     Buf<Tile> tiles;
     Buf<int32_t> counts;
     Buf<int64_t> base, seg_tile, seg_first, run_start;
@@ -220,42 +209,14 @@ struct mc_runs {
     bool computed = false;
     int64_t S = 0, n_runs = 0, n_tiles = 0;
     float ms[3] = {0, 0, 0};
-    ~mc_runs() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (pin_total) (void)hipHostFree(pin_total);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 extern "C" int mc_runs_create(int device, mc_runs** out) {
     MC_REQUIRE(out, MC_E_INVALID, "null argument");
-    *out = nullptr;
-    int n_dev = 0;
-    HIP_TRY(hipGetDeviceCount(&n_dev));
-    MC_REQUIRE(device >= 0 && device < n_dev, MC_E_HIP, "no HIP device %d (%d present)", device, n_dev);
-    HIP_TRY(hipSetDevice(device));
-    mc_runs* r = new mc_runs();
-    r->device = device;
-    bool ok = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipHostMalloc((void**)&r->pin_total, sizeof(int64_t), hipHostMallocDefault) == hipSuccess;
-    for (auto& e : r->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    if (!ok) {
-        delete r;
-        mc::set_error("HIP stream / event creation failed");
-        return MC_E_HIP;
-    }
-    *out = r;
-    return MC_OK;
+    return mc::stage_create(device, out);
 }
 
-extern "C" int mc_runs_destroy(mc_runs* r) {
-    if (r) {
-        (void)hipSetDevice(r->device);
-        delete r;
-    }
-    return MC_OK;
-}
+extern "C" int mc_runs_destroy(mc_runs* r) { return mc::stage_destroy(r); }
 
 extern "C" int mc_runs_dims(int32_t* tile, int32_t* scan_width) {
     MC_REQUIRE(tile && scan_width, MC_E_INVALID, "null argument");
@@ -277,55 +238,35 @@ extern "C" int mc_runs_compute(mc_runs* r, mc_ctx* ctx, int64_t S, const int32_t
                    "quantisation edges must be non-negative and strictly increasing (edge %d = %d)", i, edges[i]);
         E.e[i] = edges[i];
     }
-    int dev = -1;
-    if (int rc = mc_ctx_device(ctx, &dev)) return rc;
-    MC_REQUIRE(dev == r->device, MC_E_INVALID, "ctx is on device %d, the runs handle on device %d", dev,
-               r->device);
-    const int32_t* d_depth = nullptr;
-    int64_t total_len = 0;
-    if (int rc = mc_depth_device(ctx, &d_depth, &total_len)) return rc;     // MC_E_STATE: depth not computed
+    mc::DepthSource src;
+    if (int rc = src.open(ctx, r->device, "runs")) return rc;
+    const int32_t* d_depth = src.d;
     r->computed = false;
 
     // ---- tile table (host), every segment checked against the contig table
     std::vector<Tile> tiles;
     std::vector<int64_t> seg_tile((size_t)S + 1);
-    int32_t c_tid = 0;                            // the contig looked up last
-    int64_t c_off = 0, c_ext = 0;
     for (int64_t s = 0; s < S; ++s) {
-        if (s == 0 || tid[s] != c_tid) {
-            int64_t off = 0, ext = 0;
-            const int rc = mc_contig_offset(ctx, tid[s], &off, &ext);
-            MC_REQUIRE(rc != MC_E_INVALID, MC_E_INVALID, "segment %lld: tid %d out of range", (long long)s,
-                       tid[s]);
-            if (rc) return rc;
-            MC_REQUIRE(off >= 0 && ext >= 0 && off + ext <= total_len, MC_E_STATE,
-                       "contig %d lies outside the depth vector", tid[s]);
-            c_tid = tid[s], c_off = off, c_ext = ext;
-        }
-        MC_REQUIRE(start[s] >= 0 && end[s] >= start[s] && end[s] <= kMaxPos, MC_E_INVALID,
-                   "segment %lld: bad range [%lld, %lld)", (long long)s, (long long)start[s], (long long)end[s]);
+        if (int rc = src.segment(s, tid, start, end)) return rc;
         seg_tile[s] = (int64_t)tiles.size();
-        for (int64_t a = start[s]; a < end[s];) {
-            Tile t;
-            t.first = c_off + a;
-            t.rel = a;
-            const int lead = (int)((reinterpret_cast<uintptr_t>(d_depth + t.first) >> 2) & 3);
-            t.n = (int32_t)std::min<int64_t>(kTile - lead, end[s] - a);
-            t.valid = (int32_t)std::max<int64_t>(0, std::min<int64_t>(t.n, c_ext - a));
-            t.seg = (int32_t)std::min<int64_t>(s, INT32_MAX);
-            t.flags = (a == start[s] ? 1 : 0) | (a >= 1 && a - 1 < c_ext ? 2 : 0);
-            tiles.push_back(t);
-            a += t.n;
-            MC_REQUIRE(tiles.size() < (size_t)INT32_MAX, MC_E_RANGE, "more than 2^31 tiles of %d positions",
-                       kTile);
-        }
+        const int rc = mc::cut_tiles(
+            tiles, kTile, start[s], end[s], 1, [&](int64_t a) { return src.lead(src.off + a); },
+            [&](int64_t a, int64_t n) {
+                Tile t;
+                t.first = src.off + a;
+                t.rel = a;
+                t.n = (int32_t)n;
+                t.valid = (int32_t)std::max<int64_t>(0, std::min<int64_t>(n, src.ext - a));
+                t.seg = (int32_t)std::min<int64_t>(s, INT32_MAX);
+                t.flags = (a == start[s] ? 1 : 0) | (a >= 1 && a - 1 < src.ext ? 2 : 0);
+                return t;
+            });
+        if (rc) return rc;
     }
     const int64_t T = (int64_t)tiles.size();
-    seg_tile[S] = T;
-    for (int64_t s = S - 1; s >= 0; --s)          // an empty segment: the next non-empty one's first tile
-        if (end[s] == start[s]) seg_tile[s] = seg_tile[s + 1];
+    mc::close_seg_tile(seg_tile, T, start, end);
 
-    if (int rc = mc_synchronize(ctx)) return rc;  // the depth vector is complete; ours is another stream
+    if (int rc = src.ready()) return rc;
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(r->tiles.reserve((size_t)T));
     HIP_TRY(r->counts.reserve((size_t)T));
@@ -335,7 +276,7 @@ extern "C" int mc_runs_compute(mc_runs* r, mc_ctx* ctx, int64_t S, const int32_t
     hipStream_t st = r->stream;
     if (T) HIP_TRY(hipMemcpyAsync(r->tiles.p, tiles.data(), (size_t)T * sizeof(Tile), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(r->seg_tile.p, seg_tile.data(), ((size_t)S + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(r->ev[0], st));
+    if (int rc = r->mark(kEvCount)) return rc;
     if (T) {
         if (n_edges)
             hipLaunchKernelGGL(runs_count_kernel<true>, dim3((unsigned)T), dim3(kThreads), 0, st, d_depth,
@@ -345,19 +286,18 @@ extern "C" int mc_runs_compute(mc_runs* r, mc_ctx* ctx, int64_t S, const int32_t
                                r->tiles.p, E, r->counts.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(r->ev[1], st));
+    if (int rc = r->mark(kEvScan)) return rc;
     hipLaunchKernelGGL(runs_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, r->counts.p, T, r->base.p,
                        r->seg_tile.p, S, r->seg_first.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(r->ev[2], st));
-    HIP_TRY(hipMemcpyAsync(r->pin_total, r->base.p + T, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t total = *r->pin_total;
+    if (int rc = r->mark(kEvScanEnd)) return rc;
+    int64_t total = 0;
+    if (int rc = r->read_total(r->base.p + T, 0, &total)) return rc;
     MC_REQUIRE(total >= 0 && total <= T * (int64_t)kTile, MC_E_STATE, "run count %lld out of range",
                (long long)total);
     HIP_TRY(r->run_start.reserve((size_t)total));
     HIP_TRY(r->run_value.reserve((size_t)total));
-    HIP_TRY(hipEventRecord(r->ev[3], st));
+    if (int rc = r->mark(kEvEmit)) return rc;
     if (T) {
         if (n_edges)
             hipLaunchKernelGGL(runs_emit_kernel<true>, dim3((unsigned)T), dim3(kThreads), 0, st, d_depth,
@@ -367,11 +307,11 @@ extern "C" int mc_runs_compute(mc_runs* r, mc_ctx* ctx, int64_t S, const int32_t
                                r->tiles.p, E, r->base.p, r->run_start.p, r->run_value.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(r->ev[4], st));
+    if (int rc = r->mark(kEvEmitEnd)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&r->ms[0], r->ev[0], r->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&r->ms[1], r->ev[1], r->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&r->ms[2], r->ev[3], r->ev[4]));
+    if (int rc = r->elapsed(kEvCount, kEvScan, &r->ms[0])) return rc;
+    if (int rc = r->elapsed(kEvScan, kEvScanEnd, &r->ms[1])) return rc;
+    if (int rc = r->elapsed(kEvEmit, kEvEmitEnd, &r->ms[2])) return rc;
     r->S = S;
     r->n_runs = total;
     r->n_tiles = T;

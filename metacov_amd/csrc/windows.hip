@@ -63,7 +63,6 @@ constexpr int kMaxThr = 16;
 constexpr int kMaxBins = 8192;                      // 32 KiB of LDS bins
 constexpr int kHistGroups = 1024;
 constexpr int kHistFlushTiles = 1 << 17;            // an LDS bin stays below 2^31
-constexpr int64_t kMaxPos = int64_t(1) << 40;       // as mc_set_contigs' length bound
 constexpr int64_t kMaxHistCells = int64_t(1) << 27;
 
 struct Tile {
@@ -444,40 +443,10 @@ __global__ __launch_bounds__(kThreads) void windows_hist_kernel(const int32_t* _
 }  // namespace
 
 namespace {
-
-struct Contig {
-    int32_t tid = 0;
-    int64_t off = 0, ext = 0;
-    bool have = false;
-};
-
-// The checks of mc_runs_compute on segment s; the contig looked up last is kept in c.
-int check_segment(mc_ctx* ctx, int64_t total_len, int64_t s, const int32_t* tid, const int64_t* start,
-                  const int64_t* end, Contig& c) {
-    if (!c.have || tid[s] != c.tid) {
-        int64_t off = 0, ext = 0;
-        const int rc = mc_contig_offset(ctx, tid[s], &off, &ext);
-        MC_REQUIRE(rc != MC_E_INVALID, MC_E_INVALID, "segment %lld: tid %d out of range", (long long)s, tid[s]);
-        if (rc) return rc;
-        MC_REQUIRE(off >= 0 && ext >= 0 && off + ext <= total_len, MC_E_STATE,
-                   "contig %d lies outside the depth vector", tid[s]);
-        c.tid = tid[s], c.off = off, c.ext = ext, c.have = true;
-    }
-    MC_REQUIRE(start[s] >= 0 && end[s] >= start[s] && end[s] <= kMaxPos, MC_E_INVALID,
-               "segment %lld: bad range [%lld, %lld)", (long long)s, (long long)start[s], (long long)end[s]);
-    return MC_OK;
+enum { kEvTile, kEvCombine, kEvCombineEnd, kEvHist, kEvHistEnd, kEvents };   // the tile pass ends where the combine begins
 }
 
-inline int lead_at(const int32_t* d_depth, int64_t first) {
-    return (int)((reinterpret_cast<uintptr_t>(d_depth + first) >> 2) & 3);
-}
-
-}  // namespace
-
-struct mc_windows {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+struct mc_windows : mc::StageHandle<kEvents, 0> {
     Buf<Tile> tiles, htiles;
     Buf<Multi> multi;
     Buf<int64_t> seg_first, sum, ge, psum, pge;
@@ -486,40 +455,14 @@ struct mc_windows {
     int64_t S = 0, n_windows = 0, n_tiles = 0;
     int32_t n_thr = 0;
     float ms[3] = {0, 0, 0};
-    ~mc_windows() {
-        for (auto& e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 extern "C" int mc_windows_create(int device, mc_windows** out) {
     MC_REQUIRE(out, MC_E_INVALID, "null argument");
-    *out = nullptr;
-    int n_dev = 0;
-    HIP_TRY(hipGetDeviceCount(&n_dev));
-    MC_REQUIRE(device >= 0 && device < n_dev, MC_E_HIP, "no HIP device %d (%d present)", device, n_dev);
-    HIP_TRY(hipSetDevice(device));
-    mc_windows* w = new mc_windows();
-    w->device = device;
-    bool ok = hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) == hipSuccess;
-    for (auto& e : w->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    if (!ok) {
-        delete w;
-        mc::set_error("HIP stream / event creation failed");
-        return MC_E_HIP;
-    }
-    *out = w;
-    return MC_OK;
+    return mc::stage_create(device, out);
 }
 
-extern "C" int mc_windows_destroy(mc_windows* w) {
-    if (w) {
-        (void)hipSetDevice(w->device);
-        delete w;
-    }
-    return MC_OK;
-}
+extern "C" int mc_windows_destroy(mc_windows* w) { return mc::stage_destroy(w); }
 
 extern "C" int mc_windows_dims(int32_t* tile, int32_t* min_window, int32_t* max_bins, int32_t* hist_groups) {
     MC_REQUIRE(tile && min_window && max_bins && hist_groups, MC_E_INVALID, "null argument");
@@ -546,23 +489,18 @@ extern "C" int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const i
                    "thresholds must be non-negative and strictly increasing (threshold %d = %d)", i, thr[i]);
         H.t[i] = thr[i];
     }
-    int dev = -1;
-    if (int rc = mc_ctx_device(ctx, &dev)) return rc;
-    MC_REQUIRE(dev == w->device, MC_E_INVALID, "ctx is on device %d, the windows handle on device %d", dev,
-               w->device);
-    const int32_t* d_depth = nullptr;
-    int64_t total_len = 0;
-    if (int rc = mc_depth_device(ctx, &d_depth, &total_len)) return rc;     // MC_E_STATE: depth not computed
+    mc::DepthSource src;
+    if (int rc = src.open(ctx, w->device, "windows")) return rc;
+    const int32_t* d_depth = src.d;
     w->computed = false;
 
     // ---- seg_first (arithmetic), every segment checked against the contig table
     std::vector<int64_t> seg_first((size_t)S + 1);
     std::vector<int64_t> c_off((size_t)S), c_ext((size_t)S);
-    Contig c;
     seg_first[0] = 0;
     for (int64_t s = 0; s < S; ++s) {
-        if (int rc = check_segment(ctx, total_len, s, tid, start, end, c)) return rc;
-        c_off[s] = c.off, c_ext[s] = c.ext;
+        if (int rc = src.segment(s, tid, start, end)) return rc;
+        c_off[s] = src.off, c_ext[s] = src.ext;
         const int64_t len = end[s] - start[s];
         const int64_t k = len == 0 ? 0 : window == 0 ? 1 : 1 + (len - 1) / window;
         seg_first[s + 1] = seg_first[s] + k;
@@ -588,34 +526,25 @@ extern "C" int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const i
             t.valid = (int32_t)std::max<int64_t>(0, std::min<int64_t>(n, c_ext[s] - a));
             t.win = twin;
             t.flags = flags;
-            tiles.push_back(t);
+            return t;
         };
-        if (win <= kSmall) {
-            for (int64_t a = start[s]; a < end[s];) {
-                const int cap = kTile - lead_at(d_depth, c_off[s] + a);
-                const int64_t k = cap / win;      // >= 1
-                const int64_t n = std::min<int64_t>(k * win, end[s] - a);
-                push(a, n, row, (int32_t)win, 0);
-                const int64_t nw = (n + win - 1) / win;
+        const auto lead = [&](int64_t a) { return src.lead(c_off[s] + a); };
+        if (win <= kSmall) {                      // a tile holds whole windows (at least one: kSmall <= kTile - 3)
+            const int rc = mc::cut_tiles(tiles, kTile, start[s], end[s], win, lead, [&](int64_t a, int64_t n) {
+                const int64_t nw = (n + win - 1) / win, row0 = row;
                 max_nw = (int)std::max<int64_t>(max_nw, nw);
                 row += nw;
-                a += n;
-                MC_REQUIRE(tiles.size() < (size_t)INT32_MAX, MC_E_RANGE, "more than 2^31 tiles of %d positions",
-                           kTile);
-            }
+                return push(a, n, row0, (int32_t)win, 0);
+            });
+            if (rc) return rc;
         } else {
             for (int64_t wa = start[s]; wa < end[s]; wa += win, ++row) {
                 const int64_t we = std::min(wa + win, end[s]);
                 const int64_t piece0 = n_pieces;
                 const size_t tile0 = tiles.size();
-                for (int64_t a = wa; a < we;) {
-                    const int cap = kTile - lead_at(d_depth, c_off[s] + a);
-                    const int64_t n = std::min<int64_t>(cap, we - a);
-                    push(a, n, n_pieces++, kTile, 1);
-                    a += n;
-                    MC_REQUIRE(tiles.size() < (size_t)INT32_MAX, MC_E_RANGE,
-                               "more than 2^31 tiles of %d positions", kTile);
-                }
+                const int rc = mc::cut_tiles(tiles, kTile, wa, we, 1, lead,
+                                             [&](int64_t a, int64_t n) { return push(a, n, n_pieces++, kTile, 1); });
+                if (rc) return rc;
                 if (n_pieces - piece0 == 1) {     // a short last window: its row directly
                     tiles[tile0].out = row;
                     tiles[tile0].flags = 0;
@@ -629,7 +558,7 @@ extern "C" int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const i
     const int64_t T = (int64_t)tiles.size();
     const int64_t M = (int64_t)multi.size();
 
-    if (int rc = mc_synchronize(ctx)) return rc;  // the depth vector is complete; ours is another stream
+    if (int rc = src.ready()) return rc;
     HIP_TRY(hipSetDevice(w->device));
     HIP_TRY(w->tiles.reserve((size_t)T));
     HIP_TRY(w->multi.reserve((size_t)M));
@@ -646,7 +575,7 @@ extern "C" int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const i
     const uint32_t inv_win =                      // only tiles of several windows divide: 16 <= window <= kSmall
         window >= MC_WINDOWS_MIN && window <= kSmall ? (uint32_t)(((uint64_t(1) << 32) + window - 1) / window) : 0;
     const size_t lds = (size_t)max_nw * (8 + 4 * (size_t)n_thr);
-    HIP_TRY(hipEventRecord(w->ev[0], st));
+    if (int rc = w->mark(kEvTile)) return rc;
     if (T) {
         const dim3 g((unsigned)T), b(kThreads);
         if (NT == 0)
@@ -660,7 +589,7 @@ extern "C" int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const i
                                w->ge.p, w->psum.p, w->pge.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(w->ev[1], st));
+    if (int rc = w->mark(kEvCombine)) return rc;
     if (M) {
         const dim3 g((unsigned)((M + kWaves - 1) / kWaves)), b(kThreads);
         if (NT == 0)
@@ -674,10 +603,10 @@ extern "C" int mc_windows_compute(mc_windows* w, mc_ctx* ctx, int64_t S, const i
                                w->sum.p, w->ge.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(w->ev[2], st));
+    if (int rc = w->mark(kEvCombineEnd)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&w->ms[0], w->ev[0], w->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&w->ms[1], w->ev[1], w->ev[2]));
+    if (int rc = w->elapsed(kEvTile, kEvCombine, &w->ms[0])) return rc;
+    if (int rc = w->elapsed(kEvCombine, kEvCombineEnd, &w->ms[1])) return rc;
     w->S = S;
     w->n_windows = W;
     w->n_tiles = T;
@@ -730,52 +659,48 @@ extern "C" int mc_windows_hist(mc_windows* w, mc_ctx* ctx, int64_t S, const int3
     MC_REQUIRE(w && ctx, MC_E_INVALID, "null argument");
     MC_REQUIRE(S >= 0 && (S == 0 || (tid && start && end && hist)), MC_E_INVALID, "bad segment arrays");
     MC_REQUIRE(n_bins >= 1 && n_bins <= kMaxBins, MC_E_INVALID, "%d bins outside 1..%d", n_bins, kMaxBins);
-    int dev = -1;
-    if (int rc = mc_ctx_device(ctx, &dev)) return rc;
-    MC_REQUIRE(dev == w->device, MC_E_INVALID, "ctx is on device %d, the windows handle on device %d", dev,
-               w->device);
-    const int32_t* d_depth = nullptr;
-    int64_t total_len = 0;
-    if (int rc = mc_depth_device(ctx, &d_depth, &total_len)) return rc;     // MC_E_STATE: depth not computed
+    mc::DepthSource src;
+    if (int rc = src.open(ctx, w->device, "windows")) return rc;
+    const int32_t* d_depth = src.d;
     MC_REQUIRE(S * (int64_t)n_bins <= kMaxHistCells, MC_E_RANGE, "%lld segments x %d bins exceed 2^27 cells",
                (long long)S, n_bins);
     std::vector<Tile> tiles;
-    Contig c;
     for (int64_t s = 0; s < S; ++s) {
-        if (int rc = check_segment(ctx, total_len, s, tid, start, end, c)) return rc;
-        for (int64_t a = start[s]; a < end[s];) {
-            Tile t;
-            t.first = c.off + a;
-            t.out = s;
-            t.n = (int32_t)std::min<int64_t>(kTile - lead_at(d_depth, t.first), end[s] - a);
-            t.valid = (int32_t)std::max<int64_t>(0, std::min<int64_t>(t.n, c.ext - a));
-            t.win = kTile;
-            t.flags = 0;
-            tiles.push_back(t);
-            a += t.n;
-            MC_REQUIRE(tiles.size() < (size_t)INT32_MAX, MC_E_RANGE, "more than 2^31 tiles of %d positions", kTile);
-        }
+        if (int rc = src.segment(s, tid, start, end)) return rc;
+        const int rc = mc::cut_tiles(
+            tiles, kTile, start[s], end[s], 1, [&](int64_t a) { return src.lead(src.off + a); },
+            [&](int64_t a, int64_t n) {
+                Tile t;
+                t.first = src.off + a;
+                t.out = s;
+                t.n = (int32_t)n;
+                t.valid = (int32_t)std::max<int64_t>(0, std::min<int64_t>(n, src.ext - a));
+                t.win = kTile;
+                t.flags = 0;
+                return t;
+            });
+        if (rc) return rc;
     }
     const int64_t T = (int64_t)tiles.size();
     const size_t cells = (size_t)S * n_bins;
-    if (int rc = mc_synchronize(ctx)) return rc;
+    if (int rc = src.ready()) return rc;
     HIP_TRY(hipSetDevice(w->device));
     HIP_TRY(w->htiles.reserve((size_t)T));
     HIP_TRY(w->hist.reserve(cells));
     hipStream_t st = w->stream;
     if (T) HIP_TRY(hipMemcpyAsync(w->htiles.p, tiles.data(), (size_t)T * sizeof(Tile), hipMemcpyHostToDevice, st));
     if (cells) HIP_TRY(hipMemsetAsync(w->hist.p, 0, cells * 8, st));
-    HIP_TRY(hipEventRecord(w->ev[3], st));
+    if (int rc = w->mark(kEvHist)) return rc;
     if (T) {
         const int64_t per = (T + kHistGroups - 1) / kHistGroups;
         hipLaunchKernelGGL(windows_hist_kernel, dim3(kHistGroups), dim3(kThreads), (size_t)n_bins * 4, st, d_depth,
                            w->htiles.p, T, per, n_bins, w->hist.p);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(w->ev[4], st));
+    if (int rc = w->mark(kEvHistEnd)) return rc;
     if (cells) HIP_TRY(hipMemcpyAsync(hist, w->hist.p, cells * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventElapsedTime(&w->ms[2], w->ev[3], w->ev[4]));
+    if (int rc = w->elapsed(kEvHist, kEvHistEnd, &w->ms[2])) return rc;
     w->hist_done = true;
     return MC_OK;
 }
