@@ -765,6 +765,76 @@ int mc_bases_diversity_get(const mc_bases* h, int64_t first, int64_t count, int6
 int mc_bases_diversity_device(const mc_bases* h, const int64_t** d_rows, int64_t* n_windows);
 int mc_bases_diversity_timing(const mc_bases* h, float* tile_ms, float* combine_ms);
 
+/* Comparison (mc_bases_compare), a further stage over the planes of TWO
+ * handles on the device: per window the sums a metagenome user derives the
+ * identity of two samples' populations from (inStrain compare's conANI and
+ * popANI between samples) and the mean distance of their allele frequencies.
+ * MC_CMP_COLS int64 per window, all integer, exact and independent of order.
+ *
+ * Handles: a and b, on one device, both begun on the same segments: the same
+ * S and per segment the same tid, start and end, else MC_E_INVALID
+ * (mc_last_error names the first differing segment).  Their tile tables and
+ * plane layouts are then the same, mc_bases_begin's cut depending on the
+ * segments only.  a == b is allowed: con_diff = pop_diff = dist_fix = 0 and
+ * compared = covered_a = covered_b.
+ *
+ * Windows are Diversity's: window == 0 or at least MC_DIV_MIN_WINDOW, segment
+ * s owns rows [win_first[s], win_first[s + 1]) (mc_bases_compare_first),
+ * *n_windows = win_first[S] (more than 2^31: MC_E_RANGE).
+ *
+ * At plane index i, for sample x in {a, b}, let x[0..3] be its A, C, G, T
+ * counts and n_x their sum in 64 bits (DEL and N are ignored, as in
+ * Diversity), md = max(min_depth, 2), mc = max(min_count, 1),
+ * qualifies_x(v) = v >= mc and v * 10^6 >= min_ppm * n_x (each sample against
+ * its own depth), major_x the first maximum of x in channel order, minor_x
+ * the largest of the other three counts, covered_x = n_x >= md, present_x(c)
+ * = c == major_x or qualifies_x(x[c]).  The columns:
+ *   0 positions  the window's length
+ *   1 covered_a  positions with covered_a
+ *   2 covered_b  positions with covered_b
+ *   3 compared   positions covered in both
+ *   4 con_diff   compared and major_a != major_b
+ *   5 pop_diff   compared and no channel c has present_a(c) and present_b(c):
+ *                the samples share no allele (this implies con_diff)
+ *   6 snv        compared and (qualifies_a(minor_a) or qualifies_b(minor_b))
+ *   7 dist_fix   sum over the compared positions of q, below
+ * so that conANI = 1 - con_diff / compared, popANI = 1 - pop_diff / compared
+ * and the mean allele-frequency distance = dist_fix / 2^32 / compared.  q is
+ * the total-variation distance of the two allele-frequency vectors in 32.32
+ * fixed point: num = sum over c of |a[c] * n_b - b[c] * n_a|, den = 2 * n_a *
+ * n_b, q = llrint((double)num / (double)den * 2^32): one IEEE double
+ * division, round half to even; q = 0 where num == 0.  With n_a, n_b < 2^26
+ * every product is below 2^52 and num <= den < 2^53, so both conversions are
+ * exact, and q <= 2^32.  A compared position with n_a or n_b of 2^26 or more
+ * fails the call with MC_E_RANGE (mc_last_error names the lowest such plane
+ * index) and no result becomes current; a position that is not compared never
+ * raises it.  Swapping the handles swaps columns 1 and 2 and changes nothing
+ * else.
+ *
+ * The result belongs to a: its rows stay in device memory owned by a (buffers
+ * of its own that only grow; mc_bases_compare_device exposes them), on a's
+ * stream, until the next mc_bases_compare on a, or a's _add_batch, _set,
+ * _ins_set or _begin.  b is only read; the call waits for b's stream before
+ * it launches.  The sites, consensus, insertion and diversity results of
+ * either handle survive a compare, and the other way round; strand, quality
+ * and insertion tracking on either handle do not change a row.
+ *
+ * Errors: either handle before begin, and _first / _get / _device / _timing
+ * without a current result, MC_E_STATE; a null handle, handles on different
+ * devices, differing segments, negative thresholds, min_ppm > 10^6, window in
+ * 1..15 and a _get range outside [0, n_windows], MC_E_INVALID.  Device side
+ * (csrc/bases_cmp.h): Diversity's shape, one workgroup per tile reading both
+ * handles' A, C, G, T planes; zero_ms of mc_bases_compare_timing is the launch
+ * that zeroes the rows tiles share, tile_ms the tile kernel's.  No
+ * floating-point atomics. */
+#define MC_CMP_COLS 8
+int mc_bases_compare(mc_bases* a, const mc_bases* b, int64_t window, int64_t min_depth, int64_t min_count,
+                     int64_t min_ppm, int64_t* n_windows);
+int mc_bases_compare_first(const mc_bases* a, int64_t* win_first /* S + 1 */);
+int mc_bases_compare_get(const mc_bases* a, int64_t first, int64_t count, int64_t* rows /* count x 8 */);
+int mc_bases_compare_device(const mc_bases* a, const int64_t** d_rows, int64_t* n_windows);
+int mc_bases_compare_timing(const mc_bases* a, float* tile_ms, float* zero_ms);
+
 /* Insertion alleles (csrc/bases_ins.h), an opt-in stage of mc_bases, off by
  * default: with it off no launch, byte or error of the calls above changes.
  * The reference has nothing here; the contract is this library's own.

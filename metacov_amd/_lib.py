@@ -166,6 +166,12 @@ SIGNATURES = {
     "mc_bases_diversity_get": [_P, _I64, _I64, _P],
     "mc_bases_diversity_device": [_P, _PP, _PI64],
     "mc_bases_diversity_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
+    # sample comparison (csrc/bases_cmp.h)
+    "mc_bases_compare": [_P, _P, _I64, _I64, _I64, _I64, _PI64],
+    "mc_bases_compare_first": [_P, _P],
+    "mc_bases_compare_get": [_P, _I64, _I64, _P],
+    "mc_bases_compare_device": [_P, _PP, _PI64],
+    "mc_bases_compare_timing": [_P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)],
     # strand (opt-in): the reverse-strand reads' planes beside the totals
     "mc_bases_track_strand": [_P, ctypes.c_int],
     "mc_bases_add_batch_flags": [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],

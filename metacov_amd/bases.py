@@ -30,7 +30,11 @@ allele seen K times on each strand.  So are the quality sums: begin(...,
 quality=True) keeps, per channel, the sum of the counted bases' quality bytes
 and of their reads' MAPQ (quality() -> (bq, mq)); the reads then come with
 their mapq column, and sites(..., min_alt_baseq=Q, min_alt_mapq=Q) asks for an
-alternative allele whose mean qualities reach the thresholds.
+alternative allele whose mean qualities reach the thresholds.  Two counters
+begun on the same segments compare their samples: a.compare(b, window=500)
+reduces both counters' planes on the device to per-window conANI / popANI
+between the samples and the distance of their allele frequencies
+(Comparison; compare(path_a, path_b, contig) is the one-call form).
 """
 import ctypes
 
@@ -220,6 +224,63 @@ class Diversity:
 
     def pop_ani(self):
         return 1.0 - _ratio(self.pop_diff, self.compared)
+
+
+CMP_COLS = 8                        # MC_CMP_COLS
+CMP_COLUMNS = ("positions", "covered_a", "covered_b", "compared", "con_diff", "pop_diff", "snv", "dist_fix")
+
+
+class Comparison:
+    """The comparison rows of two samples over S segments
+    (BaseCounter.compare): segment s owns rows win_first[s] .. win_first[s + 1],
+    its windows in order; rows [n, 8] int64 with the columns CMP_COLUMNS, each
+    also an attribute (positions, covered_a, covered_b, compared, con_diff,
+    pop_diff, snv, dist_fix).  window: the window length asked for (0: whole
+    segments).  The ratio methods return float64 with NaN where the
+    denominator is 0."""
+
+    def __init__(self, win_first, rows, window=0):
+        self.win_first = np.asarray(win_first, np.int64)
+        self.rows = np.asarray(rows, np.int64).reshape(-1, CMP_COLS)
+        self.window = int(window)
+        for c, name in enumerate(CMP_COLUMNS):
+            setattr(self, name, self.rows[:, c])
+
+    def __len__(self):
+        return len(self.rows)
+
+    def segment(self):
+        """int64 [n]: the segment of each row."""
+        return np.repeat(np.arange(len(self.win_first) - 1, dtype=np.int64), np.diff(self.win_first))
+
+    def start(self):
+        """int64 [n]: each window's first position, counted from its segment's start."""
+        k = np.arange(len(self.rows), dtype=np.int64) - self.win_first[:-1][self.segment()]
+        return k * self.window
+
+    def end(self):
+        return self.start() + self.positions
+
+    def breadth_a(self):
+        return _ratio(self.covered_a, self.positions)
+
+    def breadth_b(self):
+        return _ratio(self.covered_b, self.positions)
+
+    def overlap(self):
+        """The share of the window's positions covered in both samples."""
+        return _ratio(self.compared, self.positions)
+
+    def con_ani(self):
+        return 1.0 - _ratio(self.con_diff, self.compared)
+
+    def pop_ani(self):
+        return 1.0 - _ratio(self.pop_diff, self.compared)
+
+    def distance(self):
+        """The mean total-variation distance of the two samples' allele
+        frequencies over the compared positions."""
+        return _ratio(self.dist_fix / PI_ONE, self.compared)
 
 
 class BaseSource:
@@ -788,6 +849,31 @@ class BaseCounter:
         check(self._lib.mc_bases_diversity_timing(self._h, ctypes.byref(a), ctypes.byref(b)), self._lib)
         return {"tile_ms": a.value, "combine_ms": b.value}
 
+    def compare(self, other, window=0, min_depth=2, min_count=1, min_ppm=0):
+        """This counter's sample against `other`'s, both begun on the same
+        segments of one device: per window of `window` positions of each
+        segment (0: per segment) the eight sums of the header's "Comparison",
+        reduced on the device from both counters' planes.  The result belongs
+        to this counter; `other` is only read.  Returns a Comparison."""
+        if not isinstance(other, BaseCounter):
+            raise TypeError("compare takes another BaseCounter")
+        n = ctypes.c_int64()
+        check(self._lib.mc_bases_compare(self._h, other._h, int(window), int(min_depth), int(min_count),
+                                         int(min_ppm), ctypes.byref(n)), self._lib)
+        n = n.value
+        first = np.zeros(self._S + 1, np.int64)
+        check(self._lib.mc_bases_compare_first(self._h, ptr(first)), self._lib)
+        rows = np.zeros((n, CMP_COLS), np.int64)
+        check(self._lib.mc_bases_compare_get(self._h, 0, n, ptr(rows)), self._lib)
+        return Comparison(first, rows, window)
+
+    def compare_timing(self):
+        """HIP-event times of the last compare call: the tile kernel, and the
+        launch in front of it that zeroes the rows tiles share."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        check(self._lib.mc_bases_compare_timing(self._h, ctypes.byref(a), ctypes.byref(b)), self._lib)
+        return {"tile_ms": a.value, "zero_ms": b.value}
+
     def timing(self):
         a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
         t, r = ctypes.c_int64(), ctypes.c_int64()
@@ -999,6 +1085,78 @@ def diversity(path, contig, start=None, stop=None, window=0, quality_threshold=0
         bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
         bc.add_bam(path, min_mapq=min_mapq, decode=decode)
         return bc.diversity(window, min_depth, min_count, min_ppm, codes)
+
+
+COMPARE_HEADER = ("#contig\tstart\tend\tpositions\tcovered_a\tcovered_b\tcompared\tcon_diff\tpop_diff\tsnv\t"
+                  "con_ani\tpop_ani\taf_dist\n")
+
+
+def write_compare(fh, names, starts, comparison, header=True):
+    """Tab-separated `contig start end positions covered_a covered_b compared
+    con_diff pop_diff snv con_ani pop_ani af_dist`, one line per window: names
+    and starts per segment (start, end 0-based, half-open, in the contig's
+    coordinates); the integers as they are, the two identities and the mean
+    allele-frequency distance '%.6f', or NA where nothing was compared.
+    Returns the lines written."""
+    if header:
+        fh.write(COMPARE_HEADER)
+    d = comparison
+    seg = d.segment()
+    a = d.start() + np.asarray(starts, np.int64).reshape(-1)[seg] if len(d) else np.zeros(0, np.int64)
+    b = a + d.positions
+
+    def fmt(v):
+        return "NA" if np.isnan(v) else "%.6f" % v
+
+    con, pop, dist = d.con_ani(), d.pop_ani(), d.distance()
+    for k, row in enumerate(d.rows.tolist()):
+        fh.write("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%s\n" % (
+            names[int(seg[k])], int(a[k]), int(b[k]), row[0], row[1], row[2], row[3], row[4], row[5], row[6],
+            fmt(con[k]), fmt(pop[k]), fmt(dist[k])))
+    return len(d)
+
+
+def same_references(path_a, refs_a, lens_a, path_b, refs_b, lens_b):
+    """None where the two headers name the same references with the same
+    lengths in the same order, else a sentence naming the first difference."""
+    if len(refs_a) != len(refs_b):
+        return "%s has %d references, %s has %d" % (path_a, len(refs_a), path_b, len(refs_b))
+    for i, (ra, la, rb, lb) in enumerate(zip(refs_a, lens_a, refs_b, lens_b)):
+        if ra != rb or la != lb:
+            return "reference %d is '%s' (%d bp) in %s and '%s' (%d bp) in %s" % (i, ra, la, path_a, rb, lb, path_b)
+    return None
+
+
+def compare(path_a, path_b, contig, start=None, stop=None, window=0, quality_threshold=0, min_mapq=0, min_depth=2,
+            min_count=1, min_ppm=0, device=0, decode="host"):
+    """The comparison rows of two BAMs over [start, stop) of one contig
+    (default: all of it) in one call: a Comparison of one segment, cut into
+    windows of `window` positions (0: one row).  Both files must have the same
+    references.  decode: as add_bam."""
+    if decode not in ("host", "gpu"):
+        raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
+    if window != 0 and window < DIV_MIN_WINDOW:
+        raise ValueError("window must be 0 or at least %d" % DIV_MIN_WINDOW)
+    lib = _lib.load()
+    with BaseSource(path_a, 0, FLAG_FILTER, min_mapq, lib) as src, \
+            BaseSource(path_b, 0, FLAG_FILTER, min_mapq, lib) as src_b:
+        diff = same_references(path_a, src.references, src.lengths, path_b, src_b.references, src_b.lengths)
+        if diff:
+            raise ValueError(diff)
+        names = [w.split()[0] if w.split() else w for w in src.references]
+        if contig not in names:
+            raise KeyError("contig '%s' is not in the header of %s" % (contig, path_a))
+        tid = names.index(contig)
+        length = src.lengths[tid]
+    start = 0 if start is None else int(start)
+    stop = length if stop is None else int(stop)
+    if start < 0 or stop < start:
+        raise ValueError("bad range [%d, %d)" % (start, stop))
+    with BaseCounter(len(names), device, lib) as bc, BaseCounter(len(names), device, lib) as other:
+        for h, path in ((bc, path_a), (other, path_b)):
+            h.begin([tid], [start], [stop], min_baseq=quality_threshold)
+            h.add_bam(path, min_mapq=min_mapq, decode=decode)
+        return bc.compare(other, window, min_depth, min_count, min_ppm)
 
 
 def consensus(path, contig, start=None, stop=None, quality_threshold=0, min_mapq=0, min_depth=1, min_count=1,

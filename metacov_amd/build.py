@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmetacov_amd.so")
 SOURCES = ["engine.hip", "ecor.hip", "scan.hip", "bam_gpu.hip", "exp_gpu.hip", "runs.hip", "windows.hip", "bases.hip", "bam_decode.cpp",
            "bam_index.cpp", "bam_write.cpp", "exp_reads.cpp", "scan_src.cpp", "bases_src.cpp", "depth_cap.cpp", "common.cpp", "runtime.cpp"]
-HEADERS = ["kernels.h", "bases_ins.h", "bases_div.h", "npstd.h", "capmask.h", "exp_gpu.h", "common.h", "bgzf.h", "inflate.h", "tile_util.h"]
+HEADERS = ["kernels.h", "bases_ins.h", "bases_div.h", "bases_cmp.h", "npstd.h", "capmask.h", "exp_gpu.h", "common.h", "bgzf.h", "inflate.h", "tile_util.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
          "-Wno-unused-function"]

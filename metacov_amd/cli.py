@@ -70,6 +70,18 @@ sum, the SNV count, the nucleotide diversity pi and, with `-f`, the consensus
 and population identity to the reference (conANI, popANI), reduced on the GPU
 from the same counts to one row per window (csrc/bases_div.h).
 
+Sample comparison (no counterpart in the reference either):
+
+    python -m metacov_amd.cli compare -b A.bam -c B.bam [-o out.tsv] [--by N] [--min-baseq 0] [--min-mapq 0]
+                                      [--min-depth 5] [--min-count 2] [--min-frac 0.05]
+                                      [-rc R.csv | -rb R.blast7] [--decode host|gpu]
+
+writes per contig, region or fixed window the positions covered in each and
+in both of two samples mapped to one reference, where their major alleles
+differ, where they share no allele (conANI and popANI between the samples)
+and the mean distance of their allele frequencies, reduced on the GPU from
+both samples' counts (csrc/bases_cmp.h).
+
 Multi-GPU (one process per GPU, SURVEY.md §8 e):
 
     python -m torch.distributed.run --nproc-per-node 8 -m metacov_amd.cli pileup -b X.bam ...
@@ -1255,6 +1267,133 @@ def diversity(bamfile, outfile, by, reference_fasta, min_baseq, min_mapq, min_de
     if counts:
         log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
                  "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    log.info("%d windows written", n)
+    if err is not None:      # the regions before a failing one are written first, as pileup does
+        raise err
+
+
+# positions per mc_bases_begin of `compare`: two handles' planes, 2 x 24 B per position on the device (derived
+# from the plane layout, not measured), cost what one `bases` group does
+COMPARE_GROUP_POSITIONS = 1 << 29
+
+
+def write_compare(path_a, path_b, references, tids, starts, ends, outfile, device=0, by=0, min_baseq=0, min_mapq=0,
+                  min_depth=5, min_count=2, min_ppm=50000, decode="host"):
+    """The comparison table of two BAMs with one header over the segments,
+    group by group as write_diversity does it, each written before the next is
+    computed: one line per segment, or per window of `by` positions.  Returns
+    (lines written, the record counts of the two sources)."""
+    from . import bases as _bases
+    import contextlib
+    names = [w.split()[0] if w.split() else w for w in references]
+    outfile.write(_bases.COMPARE_HEADER)
+    written, counts = 0, [None, None]
+    if len(tids) == 0:
+        return 0, counts
+    with contextlib.ExitStack() as stack:
+        bcs = [stack.enter_context(_bases.BaseCounter(len(references), device)) for _ in range(2)]
+        srcs = [None, None]
+        if decode == "gpu":
+            for k, path in enumerate((path_a, path_b)):
+                try:
+                    srcs[k] = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
+                except _bases._lib.MetacovError as e:
+                    if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
+                        raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
+                                                   "run with --decode host (%s)" % (path, device, e))
+                    raise
+        for a, b in depth_groups(starts, ends, COMPARE_GROUP_POSITIONS):
+            for k, path in enumerate((path_a, path_b)):
+                bcs[k].begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
+                if srcs[k] is not None:
+                    bcs[k].add_device(srcs[k])
+                    counts[k] = srcs[k].counts()
+                else:
+                    counts[k] = bcs[k].add_bam(path, min_mapq=min_mapq)
+            cmp = bcs[0].compare(bcs[1], by, min_depth, min_count, min_ppm)
+            written += _bases.write_compare(outfile, [names[int(t)] for t in tids[a:b]], starts[a:b], cmp,
+                                            header=False)
+    return written, counts
+
+
+@main.command()
+@click.option('--bamfile', '-b', type=click.File('rb'), required=True,
+              help="Sample A: input BAM file. Must be coordinate-sorted.")
+@click.option('--compare-bamfile', '-c', type=click.File('rb'), required=True,
+              help="Sample B: a BAM file with the same reference names and lengths in the same order.")
+@click.option('--outfile', '-o', type=click.File('w'), default="-",
+              help="Output table (default STDOUT)")
+@click.option('--by', type=int, default=0, metavar="N",
+              help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
+@click.option('--min-baseq', type=click.IntRange(0), default=0,
+              help="Count only bases of at least this quality")
+@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
+              help="Use only reads of at least this mapping quality")
+@click.option('--min-depth', type=click.IntRange(0), default=5, show_default=True,
+              help="A position is covered in a sample with A + C + G + T of at least this (never below 2)")
+@click.option('--min-count', type=click.IntRange(0), default=2, show_default=True,
+              help="An allele is present in a sample with this many reads ...")
+@click.option('--min-frac', type=float, default=0.05, show_default=True,
+              help="... and this fraction (0..1) of that sample's bases at the position")
+@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
+              help="Input Region file in BLAST7 format")
+@click.option('--regionfile-csv', '-rc', type=click.File('r'),
+              help="Input Region file in CSV format")
+@click.option('--device', type=int, default=0, help="HIP device ordinal")
+@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
+              help="Where the BAMs are decoded: on host threads, one pass per group of 2^29 positions, or once each "
+                   "on the GPU, the records staying in device memory (both files' reads must fit there)")
+def compare(bamfile, compare_bamfile, outfile, by, min_baseq, min_mapq, min_depth, min_count, min_frac,
+            regionfile_blast7, regionfile_csv, device, decode):
+    """
+    Compare two samples mapped to one reference: windowed conANI / popANI between them
+
+    One line `contig start end positions covered_a covered_b compared
+    con_diff pop_diff snv con_ani pop_ani af_dist` per contig in header order,
+    or per region of a region file in file order, whole (--by 0) or cut into
+    windows of N positions.  compared: positions with at least --min-depth
+    bases in both samples; con_diff: of those, the major alleles differ;
+    pop_diff: no allele is present in both samples (an allele is present in a
+    sample as its major allele or by --min-count and --min-frac); snv: a
+    second allele passes the thresholds in either sample; af_dist: the mean
+    total-variation distance of the allele frequencies.  Deletions are not
+    bases here.  Reduced on the GPU from both samples' counts; single process
+    only.
+    """
+    from . import bases as _bases
+    if regionfile_blast7 and regionfile_csv:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    if by != 0 and by < _bases.DIV_MIN_WINDOW:
+        raise click.BadParameter("must be 0 or at least %d" % _bases.DIV_MIN_WINDOW, param_hint="--by")
+    if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
+        raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
+    min_ppm = int(round(min_frac * 1e6))
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("compare runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)")
+    with _bases.BaseSource(bamfile.name) as head, _bases.BaseSource(compare_bamfile.name) as other:
+        references, lengths = list(head.references), list(head.lengths)
+        diff = _bases.same_references(bamfile.name, references, lengths, compare_bamfile.name,
+                                      list(other.references), list(other.lengths))
+    if diff:
+        raise click.ClickException("the two files do not share one reference: " + diff)
+    err = None
+    if regionfile_blast7 or regionfile_csv:
+        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
+        _, tids, starts, ends, err = resolve_regions(head, regions)
+    else:
+        tids = np.arange(len(lengths), dtype=np.int32)
+        starts = np.zeros(len(tids), np.int64)
+        ends = np.asarray(lengths, np.int64)
+    n, counts = write_compare(bamfile.name, compare_bamfile.name, references, tids, starts, ends, outfile,
+                              device=device, by=by, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
+                              min_count=min_count, min_ppm=min_ppm, decode=decode)
+    outfile.flush()
+    for label, c in zip(("A", "B"), counts):
+        if c:
+            log.info("Sample {label}, number of records:\n  total:    {records}\n  kept:     {kept}\n"
+                     "  skipped, no SEQ:           {no_seq}\n"
+                     "  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(label=label, **c))
     log.info("%d windows written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err

@@ -788,6 +788,7 @@ __global__ __launch_bounds__(kThreads) void cons_emit_kernel(const uint8_t* __re
 
 #include "bases_ins.h"   // the insertion stage's kernels
 #include "bases_div.h"   // the diversity stage's kernels
+#include "bases_cmp.h"   // the comparison stage's tile kernel
 
 constexpr size_t kArenaPad = 64;   // bytes behind every uploaded array
 
@@ -809,12 +810,14 @@ struct InsTable {
 };
 
 // The handle's timing events: a span of a *_timing call lies between two of
-// them (the consensus' call ends where its scan begins, the diversity's zero
-// pass where its tile pass begins).
+// them (the consensus' call ends where its scan begins, the diversity's and
+// the comparison's zero pass where its tile pass begins); kEvCmpWait is
+// recorded on the other handle's stream, for this one to wait on.
 enum {
     kEvPrepass, kEvPrepassEnd, kEvPileup, kEvPileupEnd, kEvSites, kEvSitesEnd,
     kEvConsCall, kEvConsScan, kEvConsScanEnd, kEvConsEmit, kEvConsEmitEnd,
     kEvDivZero, kEvDivTile, kEvDivEnd,
+    kEvCmpWait, kEvCmpZero, kEvCmpTile, kEvCmpEnd,
     kEvInsExtract, kEvInsExtractEnd, kEvInsGroup, kEvInsGroupEnd, kEvInsCons, kEvInsConsEnd,
     kEvents
 };
@@ -822,14 +825,16 @@ enum {
 }  // namespace
 
 // pin: [0] lowest bad read, [1] max span (int32), [2] site total, [3] consensus total, [4] insertion totals,
-// [7] the diversity's bad index
-struct mc_bases : mc::StageHandle<kEvents, 8> {
+// [7] the diversity's bad index, [8] the comparison's
+struct mc_bases : mc::StageHandle<kEvents, 9> {
     int32_t n_ref = 0;
     // segments and planes (mc_bases_begin)
     bool begun = false;
     int32_t min_baseq = 0;
     int64_t S = 0, N = 0, stride = 4, n_tiles = 0;
     std::vector<int64_t> seg_off;
+    std::vector<int32_t> seg_tid;        // the segments as begun, on the host (mc_bases_compare's check)
+    std::vector<int64_t> seg_start, seg_end;
     std::vector<int64_t> tile_out;       // the tiles' first plane indices, on the host (diversity, mc_bases_ins_set)
     Buf<Tile> tiles;
     Buf<int32_t> order;                  // the tiles sorted by (tid, rel)
@@ -868,6 +873,14 @@ struct mc_bases : mc::StageHandle<kEvents, 8> {
     Buf<int64_t> div_rows;               // [n_div][8]
     Buf<unsigned long long> div_bad;     // the lowest covered plane index with 2^26 bases or more (pin[7] on the host)
     float ms_div_tile = 0, ms_div_zero = 0;
+    // comparison with another handle: buffers of its own once more
+    bool have_cmp = false;
+    int64_t n_cmp = 0;                   // windows in all
+    std::vector<int64_t> cmp_first;      // [S + 1]
+    Buf<DivTile> cmp_tiles;              // [T]
+    Buf<int64_t> cmp_rows;               // [n_cmp][8]
+    Buf<unsigned long long> cmp_bad;     // the lowest compared plane index with 2^26 bases or more (pin[8] on the host)
+    float ms_cmp_tile = 0, ms_cmp_zero = 0;
     // insertions (opt-in, mc_bases_track_insertions): events, their sorted buckets, two row tables
     bool track_next = false, tracking = false;
     bool ins_from_set = false;           // mc_bases_ins_set installed the sorted buckets
@@ -943,6 +956,7 @@ void invalidate_results(mc_bases* h) {
     h->have_sites = false;
     h->have_cons = false;
     h->have_div = false;
+    h->have_cmp = false;
     invalidate_ins(h);
 }
 
@@ -984,6 +998,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->have_cons = false;
     h->have_cons_ins = false;
     h->have_div = false;
+    h->have_cmp = false;
     h->tracking = false;
     h->strand = false;
     h->have_sites_rev = false;
@@ -1067,6 +1082,9 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->stride = stride;
     h->n_tiles = T;
     h->seg_off = std::move(seg_off);
+    h->seg_tid.assign(tid, tid + S);
+    h->seg_start.assign(start, start + S);
+    h->seg_end.assign(end, end + S);
     h->tile_key = std::move(tile_key);
     h->min_baseq = min_baseq;
     h->have_last = false;
@@ -1074,6 +1092,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->ms_prepass = h->ms_pileup = h->ms_sites = 0;
     h->ms_cons_call = h->ms_cons_scan = h->ms_cons_emit = 0;
     h->ms_div_tile = h->ms_div_zero = 0;
+    h->ms_cmp_tile = h->ms_cmp_zero = 0;
     h->begun = true;
     return MC_OK;
 }
@@ -2034,6 +2053,44 @@ extern "C" int mc_bases_consensus_timing(const mc_bases* h, float* call_ms, floa
 
 // ---- diversity (the contract is the header's, "Diversity") --------------------
 
+namespace {
+
+// The windows of `window` positions over h's segments (arithmetic: first[S + 1], *n_windows) and, per tile of
+// mc_bases_begin's cut, its first window and where in it the tile starts: tile_out against seg_off is the
+// tile's offset inside its segment.  For mc_bases_diversity and mc_bases_compare.
+int div_windows(const mc_bases* h, int64_t window, std::vector<int64_t>& first, std::vector<DivTile>& dt,
+                int64_t* n_windows) {
+    const int64_t T = h->n_tiles, S = h->S;
+    first.assign((size_t)S + 1, 0);
+    int64_t nw = 0;
+    for (int64_t s = 0; s < S; ++s) {
+        first[(size_t)s] = nw;
+        const int64_t len = h->seg_off[(size_t)s + 1] - h->seg_off[(size_t)s];
+        nw += window ? (len + window - 1) / window : (len > 0);
+        MC_REQUIRE(nw <= (int64_t(1) << 31), MC_E_RANGE, "more than 2^31 windows of %lld positions",
+                   (long long)window);
+    }
+    first[(size_t)S] = nw;
+    dt.resize((size_t)T);
+    for (int64_t i = 0, s = 0; i < T; ++i) {
+        const int64_t out = h->tile_out[(size_t)i];
+        while (h->seg_off[(size_t)s + 1] <= out) ++s;       // tiles and segments ascend together; out < N
+        const int64_t p = out - h->seg_off[(size_t)s];
+        dt[(size_t)i] = window ? DivTile{first[(size_t)s] + p / window, p % window} : DivTile{first[(size_t)s], p};
+    }
+    *n_windows = nw;
+    return MC_OK;
+}
+
+// The thresholds and the window as the tile kernels take them.
+DivArgs div_args(int64_t window, int64_t min_depth, int64_t min_count, int64_t min_ppm) {
+    return DivArgs{(unsigned long long)std::max<int64_t>(min_depth, 2),
+                   (unsigned long long)std::max<int64_t>(min_count, 1), (unsigned long long)min_ppm,
+                   window ? window : 2 * kMaxPos};
+}
+
+}  // namespace
+
 extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth, int64_t min_count, int64_t min_ppm,
                                   const uint8_t* ref, int64_t* n_windows) {
     MC_REQUIRE(h && n_windows, MC_E_INVALID, "null argument");
@@ -2044,29 +2101,12 @@ extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth
     MC_REQUIRE(window == 0 || window >= MC_DIV_MIN_WINDOW, MC_E_INVALID, "window %lld: must be 0 or at least %d",
                (long long)window, MC_DIV_MIN_WINDOW);
     h->have_div = false;
-    const int64_t T = h->n_tiles, S = h->S;
-    // the windows (arithmetic) and, per tile of mc_bases_begin's cut, its first window and where in it the
-    // tile starts: tile_out against seg_off is the tile's offset inside its segment
-    std::vector<int64_t> first((size_t)S + 1);
+    const int64_t T = h->n_tiles;
+    std::vector<int64_t> first;
+    std::vector<DivTile> dt;
     int64_t nw = 0;
-    for (int64_t s = 0; s < S; ++s) {
-        first[(size_t)s] = nw;
-        const int64_t len = h->seg_off[(size_t)s + 1] - h->seg_off[(size_t)s];
-        nw += window ? (len + window - 1) / window : (len > 0);
-        MC_REQUIRE(nw <= (int64_t(1) << 31), MC_E_RANGE, "more than 2^31 windows of %lld positions",
-                   (long long)window);
-    }
-    first[(size_t)S] = nw;
-    std::vector<DivTile> dt((size_t)T);
-    for (int64_t i = 0, s = 0; i < T; ++i) {
-        const int64_t out = h->tile_out[(size_t)i];
-        while (h->seg_off[(size_t)s + 1] <= out) ++s;       // tiles and segments ascend together; out < N
-        const int64_t p = out - h->seg_off[(size_t)s];
-        dt[(size_t)i] = window ? DivTile{first[(size_t)s] + p / window, p % window} : DivTile{first[(size_t)s], p};
-    }
-    const DivArgs da{(unsigned long long)std::max<int64_t>(min_depth, 2),
-                     (unsigned long long)std::max<int64_t>(min_count, 1), (unsigned long long)min_ppm,
-                     window ? window : 2 * kMaxPos};
+    if (int rc = div_windows(h, window, first, dt, &nw)) return rc;
+    const DivArgs da = div_args(window, min_depth, min_count, min_ppm);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(h->div_tiles.reserve((size_t)T));
     HIP_TRY(h->div_rows.reserve((size_t)(nw * kDivCols)));
@@ -2138,6 +2178,113 @@ extern "C" int mc_bases_diversity_timing(const mc_bases* h, float* tile_ms, floa
     MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
     *tile_ms = h->ms_div_tile;
     *combine_ms = h->ms_div_zero;
+    return MC_OK;
+}
+
+// ---- comparison (the contract is the header's, "Comparison") ------------------
+
+extern "C" int mc_bases_compare(mc_bases* a, const mc_bases* b, int64_t window, int64_t min_depth, int64_t min_count,
+                                int64_t min_ppm, int64_t* n_windows) {
+    MC_REQUIRE(a && b && n_windows, MC_E_INVALID, "null argument");
+    MC_REQUIRE(a->begun && b->begun, MC_E_STATE, "no segments on %s (call mc_bases_begin)",
+               a->begun ? "the second handle" : "the first handle");
+    MC_REQUIRE(a->device == b->device, MC_E_INVALID, "the handles are on devices %d and %d", a->device, b->device);
+    MC_REQUIRE(a->S == b->S, MC_E_INVALID, "segment %lld: the handles have %lld and %lld segments",
+               (long long)std::min(a->S, b->S), (long long)a->S, (long long)b->S);
+    for (int64_t s = 0; s < a->S; ++s) {
+        const size_t k = (size_t)s;
+        MC_REQUIRE(a->seg_tid[k] == b->seg_tid[k] && a->seg_start[k] == b->seg_start[k] &&
+                       a->seg_end[k] == b->seg_end[k],
+                   MC_E_INVALID, "segment %lld differs: tid %d [%lld, %lld) against tid %d [%lld, %lld)", (long long)s,
+                   a->seg_tid[k], (long long)a->seg_start[k], (long long)a->seg_end[k], b->seg_tid[k],
+                   (long long)b->seg_start[k], (long long)b->seg_end[k]);
+    }
+    MC_REQUIRE(min_depth >= 0 && min_count >= 0 && min_ppm >= 0 && min_ppm <= 1000000, MC_E_INVALID,
+               "comparison thresholds out of range (min_depth %lld, min_count %lld, min_ppm %lld of 10^6)",
+               (long long)min_depth, (long long)min_count, (long long)min_ppm);
+    MC_REQUIRE(window == 0 || window >= MC_DIV_MIN_WINDOW, MC_E_INVALID, "window %lld: must be 0 or at least %d",
+               (long long)window, MC_DIV_MIN_WINDOW);
+    a->have_cmp = false;
+    const int64_t T = a->n_tiles;
+    std::vector<int64_t> first;
+    std::vector<DivTile> dt;
+    int64_t nw = 0;
+    if (int rc = div_windows(a, window, first, dt, &nw)) return rc;
+    const DivArgs da = div_args(window, min_depth, min_count, min_ppm);
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(a->cmp_tiles.reserve((size_t)T));
+    HIP_TRY(a->cmp_rows.reserve((size_t)(nw * kCmpCols)));
+    HIP_TRY(a->cmp_bad.reserve(1));
+    hipStream_t st = a->stream;
+    if (a != b) {                                 // b's planes may still be in flight on its stream
+        HIP_TRY(hipEventRecord(a->ev[kEvCmpWait], b->stream));
+        HIP_TRY(hipStreamWaitEvent(st, a->ev[kEvCmpWait], 0));
+    }
+    a->pin[8] = kNoBad;
+    HIP_TRY(hipMemcpyAsync(a->cmp_bad.p, a->pin + 8, 8, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(a->cmp_tiles.p, dt.data(), (size_t)T * sizeof(DivTile), hipMemcpyHostToDevice, st));
+    if (int rc = a->mark(kEvCmpZero)) return rc;
+    if (T) {
+        hipLaunchKernelGGL(div_zero_kernel, dim3((unsigned)((T * 16 + 255) / 256)), dim3(256), 0, st, a->tiles.p,
+                           a->cmp_tiles.p, T, da.window, a->cmp_rows.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = a->mark(kEvCmpTile)) return rc;
+    if (T) {
+        hipLaunchKernelGGL(cmp_tile_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, a->planes.p, a->stride,
+                           b->planes.p, b->stride, a->tiles.p, a->cmp_tiles.p, da, a->cmp_rows.p, a->cmp_bad.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = a->mark(kEvCmpEnd)) return rc;
+    HIP_TRY(hipMemcpyAsync(a->pin + 8, a->cmp_bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));            // (dt is released)
+    const unsigned long long bad = a->pin[8];
+    MC_REQUIRE(bad == kNoBad, MC_E_RANGE,
+               "plane index %llu: A + C + G + T of a compared position is 2^26 or more in one of the samples "
+               "(dist_fix is exact below that)",
+               bad);
+    if (int rc = a->elapsed(kEvCmpZero, kEvCmpTile, &a->ms_cmp_zero)) return rc;
+    if (int rc = a->elapsed(kEvCmpTile, kEvCmpEnd, &a->ms_cmp_tile)) return rc;
+    a->cmp_first = std::move(first);
+    a->n_cmp = nw;
+    a->have_cmp = true;
+    *n_windows = nw;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_compare_first(const mc_bases* a, int64_t* win_first) {
+    MC_REQUIRE(a && win_first, MC_E_INVALID, "null argument");
+    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
+    std::memcpy(win_first, a->cmp_first.data(), a->cmp_first.size() * 8);
+    return MC_OK;
+}
+
+extern "C" int mc_bases_compare_get(const mc_bases* a, int64_t first, int64_t count, int64_t* rows) {
+    MC_REQUIRE(a, MC_E_INVALID, "null argument");
+    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
+    if (int rc = check_range(first, count, a->n_cmp, "windows")) return rc;
+    MC_REQUIRE(count == 0 || rows, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(a->device));
+    HIP_TRY(hipMemcpyAsync(rows, a->cmp_rows.p + first * kCmpCols, (size_t)count * kCmpCols * 8,
+                           hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    return MC_OK;
+}
+
+extern "C" int mc_bases_compare_device(const mc_bases* a, const int64_t** d_rows, int64_t* n_windows) {
+    MC_REQUIRE(a && d_rows && n_windows, MC_E_INVALID, "null argument");
+    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
+    *d_rows = a->cmp_rows.p;
+    *n_windows = a->n_cmp;
+    return MC_OK;
+}
+
+extern "C" int mc_bases_compare_timing(const mc_bases* a, float* tile_ms, float* zero_ms) {
+    MC_REQUIRE(a && tile_ms && zero_ms, MC_E_INVALID, "null argument");
+    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
+    *tile_ms = a->ms_cmp_tile;
+    *zero_ms = a->ms_cmp_zero;
     return MC_OK;
 }
 
@@ -2255,6 +2402,7 @@ extern "C" int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const 
     invalidate_ins(h);
     h->have_cons = false;
     h->have_div = false;
+    h->have_cmp = false;
     HIP_TRY(h->ins_sorted.reserve((size_t)n));
     HIP_TRY(h->ins_weight.reserve((size_t)n));
     HIP_TRY(h->ins_bbase.reserve((size_t)T + 1));
