@@ -49,6 +49,12 @@ FLAG_FILTER = 0x704
 GET_CHUNK = 1 << 22                 # positions per mc_bases_get of write_all
 
 
+def contig_names(references):
+    """The contig id of each header name: its first word, or the name itself
+    where it has no word."""
+    return [w.split()[0] if w.split() else w for w in references]
+
+
 def dims(lib=None):
     """Tile positions of the pileup kernel."""
     lib = lib or _lib.load()
@@ -175,19 +181,18 @@ def _ratio(num, den):
     return out
 
 
-class Diversity:
-    """The diversity rows of S segments (BaseCounter.diversity): segment s owns
-    rows win_first[s] .. win_first[s + 1], its windows in order; rows [n, 8]
-    int64 with the columns DIV_COLUMNS, each also an attribute (positions,
-    covered, bases, snv, pi_fix, compared, con_diff, pop_diff).  window: the
-    window length asked for (0: whole segments).  The ratio methods return
-    float64 with NaN where the denominator is 0."""
+class _WindowRows:
+    """What Diversity and Comparison share: segment s owns rows win_first[s] ..
+    win_first[s + 1], its windows in order; rows [n, 8] int64 with the class's
+    COLUMNS, each also an attribute; window: the window length asked for (0:
+    whole segments).  Both have the columns compared, con_diff and pop_diff."""
+    COLUMNS = ()
 
     def __init__(self, win_first, rows, window=0):
         self.win_first = np.asarray(win_first, np.int64)
-        self.rows = np.asarray(rows, np.int64).reshape(-1, DIV_COLS)
+        self.rows = np.asarray(rows, np.int64).reshape(-1, len(self.COLUMNS))
         self.window = int(window)
-        for c, name in enumerate(DIV_COLUMNS):
+        for c, name in enumerate(self.COLUMNS):
             setattr(self, name, self.rows[:, c])
 
     def __len__(self):
@@ -204,6 +209,22 @@ class Diversity:
 
     def end(self):
         return self.start() + self.positions
+
+    def con_ani(self):
+        return 1.0 - _ratio(self.con_diff, self.compared)
+
+    def pop_ani(self):
+        return 1.0 - _ratio(self.pop_diff, self.compared)
+
+
+class Diversity(_WindowRows):
+    """The diversity rows of S segments (BaseCounter.diversity): segment s owns
+    rows win_first[s] .. win_first[s + 1], its windows in order; rows [n, 8]
+    int64 with the columns DIV_COLUMNS, each also an attribute (positions,
+    covered, bases, snv, pi_fix, compared, con_diff, pop_diff).  window: the
+    window length asked for (0: whole segments).  The ratio methods return
+    float64 with NaN where the denominator is 0."""
+    COLUMNS = DIV_COLUMNS
 
     def pi(self):
         """Nucleotide diversity: the mean over the covered positions."""
@@ -219,18 +240,12 @@ class Diversity:
     def snv_density(self):
         return _ratio(self.snv, self.covered)
 
-    def con_ani(self):
-        return 1.0 - _ratio(self.con_diff, self.compared)
-
-    def pop_ani(self):
-        return 1.0 - _ratio(self.pop_diff, self.compared)
-
 
 CMP_COLS = 8                        # MC_CMP_COLS
 CMP_COLUMNS = ("positions", "covered_a", "covered_b", "compared", "con_diff", "pop_diff", "snv", "dist_fix")
 
 
-class Comparison:
+class Comparison(_WindowRows):
     """The comparison rows of two samples over S segments
     (BaseCounter.compare): segment s owns rows win_first[s] .. win_first[s + 1],
     its windows in order; rows [n, 8] int64 with the columns CMP_COLUMNS, each
@@ -238,28 +253,7 @@ class Comparison:
     pop_diff, snv, dist_fix).  window: the window length asked for (0: whole
     segments).  The ratio methods return float64 with NaN where the
     denominator is 0."""
-
-    def __init__(self, win_first, rows, window=0):
-        self.win_first = np.asarray(win_first, np.int64)
-        self.rows = np.asarray(rows, np.int64).reshape(-1, CMP_COLS)
-        self.window = int(window)
-        for c, name in enumerate(CMP_COLUMNS):
-            setattr(self, name, self.rows[:, c])
-
-    def __len__(self):
-        return len(self.rows)
-
-    def segment(self):
-        """int64 [n]: the segment of each row."""
-        return np.repeat(np.arange(len(self.win_first) - 1, dtype=np.int64), np.diff(self.win_first))
-
-    def start(self):
-        """int64 [n]: each window's first position, counted from its segment's start."""
-        k = np.arange(len(self.rows), dtype=np.int64) - self.win_first[:-1][self.segment()]
-        return k * self.window
-
-    def end(self):
-        return self.start() + self.positions
+    COLUMNS = CMP_COLUMNS
 
     def breadth_a(self):
         return _ratio(self.covered_a, self.positions)
@@ -270,12 +264,6 @@ class Comparison:
     def overlap(self):
         """The share of the window's positions covered in both samples."""
         return _ratio(self.compared, self.positions)
-
-    def con_ani(self):
-        return 1.0 - _ratio(self.con_diff, self.compared)
-
-    def pop_ani(self):
-        return 1.0 - _ratio(self.pop_diff, self.compared)
 
     def distance(self):
         """The mean total-variation distance of the two samples' allele
@@ -664,6 +652,25 @@ class BaseCounter:
         check(self._lib.mc_bases_get_quality(self._h, int(first), int(count), ptr(bq), ptr(mq)), self._lib)
         return bq, mq
 
+    def _ref_plane(self, ref):
+        """ref (None, or uint8 [N] codes) as the library takes it: contiguous,
+        one entry per position."""
+        if ref is None:
+            return None
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        if len(ref) != int(self.seg_off[-1]):
+            raise ValueError("the reference plane must have one entry per position")
+        return ref
+
+    def _window_rows(self, first_fn, get_fn, n, cols):
+        """(win_first, rows [n, cols]) of a window-row result through its
+        mc_bases_*_first and mc_bases_*_get."""
+        first = np.zeros(self._S + 1, np.int64)
+        check(first_fn(self._h, ptr(first)), self._lib)
+        rows = np.zeros((n, cols), np.int64)
+        check(get_fn(self._h, 0, n, ptr(rows)), self._lib)
+        return first, rows
+
     def sites(self, min_depth=1, min_count=1, min_ppm=0, ref=None, min_alt_strand=0, min_alt_baseq=0,
               min_alt_mapq=0):
         """The sites among the positions (see the header); ref: optional uint8
@@ -681,10 +688,7 @@ class BaseCounter:
         if (min_alt_baseq or min_alt_mapq) and not self._quality:
             raise ValueError("min_alt_baseq / min_alt_mapq need a counter that tracks quality "
                              "(begin(..., quality=True))")
-        if ref is not None:
-            ref = np.ascontiguousarray(ref, dtype=np.uint8)
-            if len(ref) != int(self.seg_off[-1]):
-                raise ValueError("the reference plane must have one entry per position")
+        ref = self._ref_plane(ref)
         n = ctypes.c_int64()
         if self._quality:
             check(self._lib.mc_bases_sites_quality(self._h, int(min_depth), int(min_count), int(min_ppm),
@@ -784,10 +788,7 @@ class BaseCounter:
         insertions: the called insertion alleles follow their anchor's letter
         in the compact output (needs begin(..., insertions=True)).
         Returns a Consensus; its letters stay on the device until fetched."""
-        if ref is not None:
-            ref = np.ascontiguousarray(ref, dtype=np.uint8)
-            if len(ref) != int(self.seg_off[-1]):
-                raise ValueError("the reference plane must have one entry per position")
+        ref = self._ref_plane(ref)
         flags = (CONS_IUPAC if iupac else 0) | (CONS_FILL_REF if fill_ref else 0) | (CONS_INS if insertions else 0)
         n = ctypes.c_int64()
         # (an empty plane still counts as given: FILL_REF with N == 0 is valid)
@@ -828,19 +829,12 @@ class BaseCounter:
         the eight sums of the header's "Diversity", reduced on the device;
         ref: optional uint8 [N] codes as sites takes them.  Returns a
         Diversity."""
-        if ref is not None:
-            ref = np.ascontiguousarray(ref, dtype=np.uint8)
-            if len(ref) != int(self.seg_off[-1]):
-                raise ValueError("the reference plane must have one entry per position")
+        ref = self._ref_plane(ref)
         n = ctypes.c_int64()
         check(self._lib.mc_bases_diversity(self._h, int(window), int(min_depth), int(min_count), int(min_ppm),
                                            ptr(ref), ctypes.byref(n)), self._lib)
-        n = n.value
-        first = np.zeros(self._S + 1, np.int64)
-        check(self._lib.mc_bases_diversity_first(self._h, ptr(first)), self._lib)
-        rows = np.zeros((n, DIV_COLS), np.int64)
-        check(self._lib.mc_bases_diversity_get(self._h, 0, n, ptr(rows)), self._lib)
-        return Diversity(first, rows, window)
+        return Diversity(*self._window_rows(self._lib.mc_bases_diversity_first, self._lib.mc_bases_diversity_get,
+                                            n.value, DIV_COLS), window)
 
     def diversity_timing(self):
         """HIP-event times of the last diversity call: the tile kernel, and
@@ -860,12 +854,8 @@ class BaseCounter:
         n = ctypes.c_int64()
         check(self._lib.mc_bases_compare(self._h, other._h, int(window), int(min_depth), int(min_count),
                                          int(min_ppm), ctypes.byref(n)), self._lib)
-        n = n.value
-        first = np.zeros(self._S + 1, np.int64)
-        check(self._lib.mc_bases_compare_first(self._h, ptr(first)), self._lib)
-        rows = np.zeros((n, CMP_COLS), np.int64)
-        check(self._lib.mc_bases_compare_get(self._h, 0, n, ptr(rows)), self._lib)
-        return Comparison(first, rows, window)
+        return Comparison(*self._window_rows(self._lib.mc_bases_compare_first, self._lib.mc_bases_compare_get,
+                                             n.value, CMP_COLS), window)
 
     def compare_timing(self):
         """HIP-event times of the last compare call: the tile kernel, and the
@@ -890,8 +880,21 @@ def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, mi
     if decode not in ("host", "gpu"):
         raise ValueError("decode must be 'host' or 'gpu', not %r" % (decode,))
     lib = _lib.load()
+    names, tid, start, stop, _ = _one_segment(path, contig, start, stop, min_mapq, lib)
+    with BaseCounter(len(names), device, lib) as bc:
+        bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
+        bc.add_bam(path, min_mapq=min_mapq, decode=decode)
+        planes = bc.counts()
+    return planes[A].copy(), planes[C].copy(), planes[G].copy(), planes[T].copy()
+
+
+def _one_segment(path, contig, start, stop, min_mapq, lib, ref=None):
+    """What the one-call functions make of their arguments: (names, tid,
+    start, stop, codes) of [start, stop) of `contig` in path's header (default:
+    all of it); codes: the reference plane of ref, ASCII letters (str, bytes or
+    uint8) of the same range, or None."""
     with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
-        names = [w.split()[0] if w.split() else w for w in src.references]
+        names = contig_names(src.references)
         if contig not in names:
             raise KeyError("contig '%s' is not in the header of %s" % (contig, path))
         tid = names.index(contig)
@@ -900,11 +903,14 @@ def count_coverage(path, contig, start=None, stop=None, quality_threshold=15, mi
     stop = length if stop is None else int(stop)
     if start < 0 or stop < start:
         raise ValueError("bad range [%d, %d)" % (start, stop))
-    with BaseCounter(len(names), device, lib) as bc:
-        bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
-        bc.add_bam(path, min_mapq=min_mapq, decode=decode)
-        planes = bc.counts()
-    return planes[A].copy(), planes[C].copy(), planes[G].copy(), planes[T].copy()
+    codes = None
+    if ref is not None:
+        if isinstance(ref, str):
+            ref = ref.encode("ascii")
+        codes = ref_codes(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref)
+        if len(codes) != stop - start:
+            raise ValueError("ref must have stop - start letters")
+    return names, tid, start, stop, codes
 
 
 # ------------------------------------------------------------------ output
@@ -1035,21 +1041,26 @@ def write_diversity(fh, names, starts, diversity, header=True):
     per segment (start, end 0-based, half-open, in the contig's coordinates);
     the integers as they are, pi and the two identities '%.6f', or NA where
     their denominator is 0.  Returns the lines written."""
-    if header:
-        fh.write(DIVERSITY_HEADER)
     d = diversity
+    return _write_window_rows(fh, DIVERSITY_HEADER if header else None, names, starts, d,
+                              [0, 1, 2, 3, d.pi(), 5, 6, 7, d.con_ani(), d.pop_ani()])
+
+
+def _write_window_rows(fh, header, names, starts, d, columns):
+    """The table of write_diversity and write_compare: `header` (or None),
+    then per row of d `contig start end` and the columns, each an index into
+    the row (an integer as it is) or a float64 array with one value per row
+    ('%.6f', or NA for NaN).  Returns the lines written."""
+    if header:
+        fh.write(header)
     seg = d.segment()
     a = d.start() + np.asarray(starts, np.int64).reshape(-1)[seg] if len(d) else np.zeros(0, np.int64)
     b = a + d.positions
-
-    def fmt(v):
-        return "NA" if np.isnan(v) else "%.6f" % v
-
-    pi, con, pop = d.pi(), d.con_ani(), d.pop_ani()
-    for k, row in enumerate(d.rows.tolist()):
-        fh.write("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%s\t%s\n" % (
-            names[int(seg[k])], int(a[k]), int(b[k]), row[0], row[1], row[2], row[3], fmt(pi[k]), row[5], row[6],
-            row[7], fmt(con[k]), fmt(pop[k])))
+    line = "%s\t%d\t%d" + "".join("\t%d" if isinstance(c, int) else "\t%s" for c in columns) + "\n"
+    cells = [d.rows[:, c].tolist() if isinstance(c, int) else ["NA" if np.isnan(v) else "%.6f" % v for v in c]
+             for c in columns]
+    for k, row in enumerate(zip(*cells)):
+        fh.write(line % ((names[int(seg[k])], int(a[k]), int(b[k])) + row))
     return len(d)
 
 
@@ -1064,23 +1075,7 @@ def diversity(path, contig, start=None, stop=None, window=0, quality_threshold=0
     if window != 0 and window < DIV_MIN_WINDOW:
         raise ValueError("window must be 0 or at least %d" % DIV_MIN_WINDOW)
     lib = _lib.load()
-    with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
-        names = [w.split()[0] if w.split() else w for w in src.references]
-        if contig not in names:
-            raise KeyError("contig '%s' is not in the header of %s" % (contig, path))
-        tid = names.index(contig)
-        length = src.lengths[tid]
-    start = 0 if start is None else int(start)
-    stop = length if stop is None else int(stop)
-    if start < 0 or stop < start:
-        raise ValueError("bad range [%d, %d)" % (start, stop))
-    codes = None
-    if ref is not None:
-        if isinstance(ref, str):
-            ref = ref.encode("ascii")
-        codes = ref_codes(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref)
-        if len(codes) != stop - start:
-            raise ValueError("ref must have stop - start letters")
+    names, tid, start, stop, codes = _one_segment(path, contig, start, stop, min_mapq, lib, ref)
     with BaseCounter(len(names), device, lib) as bc:
         bc.begin([tid], [start], [stop], min_baseq=quality_threshold)
         bc.add_bam(path, min_mapq=min_mapq, decode=decode)
@@ -1098,22 +1093,9 @@ def write_compare(fh, names, starts, comparison, header=True):
     coordinates); the integers as they are, the two identities and the mean
     allele-frequency distance '%.6f', or NA where nothing was compared.
     Returns the lines written."""
-    if header:
-        fh.write(COMPARE_HEADER)
     d = comparison
-    seg = d.segment()
-    a = d.start() + np.asarray(starts, np.int64).reshape(-1)[seg] if len(d) else np.zeros(0, np.int64)
-    b = a + d.positions
-
-    def fmt(v):
-        return "NA" if np.isnan(v) else "%.6f" % v
-
-    con, pop, dist = d.con_ani(), d.pop_ani(), d.distance()
-    for k, row in enumerate(d.rows.tolist()):
-        fh.write("%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\t%s\t%s\n" % (
-            names[int(seg[k])], int(a[k]), int(b[k]), row[0], row[1], row[2], row[3], row[4], row[5], row[6],
-            fmt(con[k]), fmt(pop[k]), fmt(dist[k])))
-    return len(d)
+    return _write_window_rows(fh, COMPARE_HEADER if header else None, names, starts, d,
+                              [0, 1, 2, 3, 4, 5, 6, d.con_ani(), d.pop_ani(), d.distance()])
 
 
 def same_references(path_a, refs_a, lens_a, path_b, refs_b, lens_b):
@@ -1143,15 +1125,7 @@ def compare(path_a, path_b, contig, start=None, stop=None, window=0, quality_thr
         diff = same_references(path_a, src.references, src.lengths, path_b, src_b.references, src_b.lengths)
         if diff:
             raise ValueError(diff)
-        names = [w.split()[0] if w.split() else w for w in src.references]
-        if contig not in names:
-            raise KeyError("contig '%s' is not in the header of %s" % (contig, path_a))
-        tid = names.index(contig)
-        length = src.lengths[tid]
-    start = 0 if start is None else int(start)
-    stop = length if stop is None else int(stop)
-    if start < 0 or stop < start:
-        raise ValueError("bad range [%d, %d)" % (start, stop))
+    names, tid, start, stop, _ = _one_segment(path_a, contig, start, stop, min_mapq, lib)
     with BaseCounter(len(names), device, lib) as bc, BaseCounter(len(names), device, lib) as other:
         for h, path in ((bc, path_a), (other, path_b)):
             h.begin([tid], [start], [stop], min_baseq=quality_threshold)
@@ -1173,23 +1147,7 @@ def consensus(path, contig, start=None, stop=None, quality_threshold=0, min_mapq
     if insertions and aligned:
         raise ValueError("insertions has no place in the aligned output")
     lib = _lib.load()
-    with BaseSource(path, 0, FLAG_FILTER, min_mapq, lib) as src:
-        names = [w.split()[0] if w.split() else w for w in src.references]
-        if contig not in names:
-            raise KeyError("contig '%s' is not in the header of %s" % (contig, path))
-        tid = names.index(contig)
-        length = src.lengths[tid]
-    start = 0 if start is None else int(start)
-    stop = length if stop is None else int(stop)
-    if start < 0 or stop < start:
-        raise ValueError("bad range [%d, %d)" % (start, stop))
-    codes = None
-    if ref is not None:
-        if isinstance(ref, str):
-            ref = ref.encode("ascii")
-        codes = ref_codes(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref)
-        if len(codes) != stop - start:
-            raise ValueError("ref must have stop - start letters")
+    names, tid, start, stop, codes = _one_segment(path, contig, start, stop, min_mapq, lib, ref)
     with BaseCounter(len(names), device, lib) as bc:
         bc.begin([tid], [start], [stop], min_baseq=quality_threshold, insertions=insertions)
         bc.add_bam(path, min_mapq=min_mapq, decode=decode)

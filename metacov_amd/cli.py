@@ -126,6 +126,7 @@ def _prewarm_hip():
 if __name__ == "__main__":
     _prewarm_hip()
 
+import contextlib  # noqa: E402
 import csv  # noqa: E402
 import json  # noqa: E402
 import logging  # noqa: E402
@@ -133,7 +134,8 @@ import logging  # noqa: E402
 import click  # noqa: E402
 import numpy as np  # noqa: E402
 
-from . import depthcap as _depthcap  # noqa: E402
+from . import bases as _bases  # noqa: E402
+from . import depthcap as _depthcap
 from . import experimental as _experimental
 from . import regions as _regions
 from . import scan as _scan
@@ -154,6 +156,93 @@ def main():
     MetaCov estimates abundance values from the stacking depth of
     reads mapped to a reference.
     """
+
+
+# ---- what the commands besides `pileup` and `scan` share: options, checks, segments ----
+
+def _options(*options):
+    """One decorator from several; --help lists them in the order given."""
+    def decorate(f):
+        for option in reversed(options):
+            f = option(f)
+        return f
+    return decorate
+
+
+_opt_regions = _options(
+    click.option('--regionfile-blast7', '-rb', type=click.File('r'), help="Input Region file in BLAST7 format"),
+    click.option('--regionfile-csv', '-rc', type=click.File('r'), help="Input Region file in CSV format"))
+_opt_by = click.option('--by', type=int, default=0, metavar="N",
+                       help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
+_opt_device = click.option('--device', type=int, default=0, help="HIP device ordinal")
+# --device --decode --legacy-endpos of `depth` and `coverage`: the engine's decoders
+_opt_engine = _options(
+    _opt_device,
+    click.option('--decode', type=click.Choice(['gpu', 'host']), default='gpu',
+                 help="gpu (default): BGZF inflate and record parse on the device; "
+                      "host: the C++ decoder on host threads"),
+    click.option('--legacy-endpos', is_flag=True, default=False,
+                 help="Count a mapped read without reference-consuming CIGAR ops on one column "
+                      "(htslib <= 1.9 bam_endpos); default: it adds nothing (current htslib)"))
+
+
+def _opt_floors(baseq_help):
+    """--min-baseq (with the command's wording) and --min-mapq."""
+    return _options(click.option('--min-baseq', type=click.IntRange(0), default=0, help=baseq_help),
+                    click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
+                                 help="Use only reads of at least this mapping quality"))
+
+
+def _opt_counter(decode_help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or "
+                             "once on the GPU, the records staying in device memory (the file's reads must fit "
+                             "there)"):
+    """--device and --decode of the base-counter commands."""
+    return _options(_opt_device, click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
+                                              help=decode_help))
+
+
+def _one_region_file(rb, rc):
+    if rb and rc:
+        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+
+
+def _ppm(frac, hint):
+    """A fraction option as parts per million; refused outside [0, 1] (nan fails both comparisons)."""
+    if not 0.0 <= frac <= 1.0:
+        raise click.BadParameter("must lie in [0, 1]", param_hint=hint)
+    return int(round(frac * 1e6))
+
+
+def _window_at_least(by):
+    """--by of `diversity` and `compare`."""
+    if by != 0 and by < _bases.DIV_MIN_WINDOW:
+        raise click.BadParameter("must be 0 or at least %d" % _bases.DIV_MIN_WINDOW, param_hint="--by")
+
+
+def _single_process(name):
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise click.UsageError("%s runs in one process (WORLD_SIZE > 1 is not supported: "
+                               "its output is not sharded)" % name)
+
+
+def _select_segments(header, rb, rc):
+    """The segments (header contig ids) a command works through: the regions
+    of a region file up to the first failing one, else every contig whole.
+    Returns (tids, starts, ends, err, from_regions); the caller raises err
+    after it has written those segments, as pileup does."""
+    if rb or rc:
+        _, tids, starts, ends, err = resolve_regions(header, _regions.make_region_iterator(rb, rc, header))
+        return tids, starts, ends, err, True
+    tids = np.arange(len(header.lengths), dtype=np.int32)
+    return tids, np.zeros(len(tids), np.int64), np.asarray(header.lengths, np.int64), None, False
+
+
+def _log_record_counts(counts, label=None):
+    """A base source's record counts (None: nothing was read), logged under the calling command's name."""
+    if counts:
+        log.info(("Sample %s, number" % label if label else "Number") +
+                 " of records:\n  total:    {records}\n  kept:     {kept}\n  skipped, no SEQ:           {no_seq}\n"
+                 "  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts), stacklevel=2)
 
 
 @main.command()
@@ -576,7 +665,7 @@ def write_depth(bam, tids, starts, ends, outfile, device=0, quantize=None, zero=
         return 0
     eng = bam.engine(device)
     local = np.asarray(bam.local_tid(tids), np.int32)
-    names = [w.split()[0] if w.split() else w for w in bam.references]
+    names = _bases.contig_names(bam.references)
     written = 0
     for a, b in depth_groups(starts, ends):
         r = eng.depth_runs(local[a:b], starts[a:b], ends[a:b], quantize=edges)
@@ -590,22 +679,13 @@ def write_depth(bam, tids, starts, ends, outfile, device=0, quantize=None, zero=
               help="Input BAM file. Must be coordinate-sorted.")
 @click.option('--outfile', '-o', type=click.File('w'), default="-",
               help="Output bedGraph (default STDOUT)")
-@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
-              help="Input Region file in BLAST7 format")
-@click.option('--regionfile-csv', '-rc', type=click.File('r'),
-              help="Input Region file in CSV format")
+@_opt_regions
 @click.option('--quantize', metavar="SPEC",
               help="Depth classes in mosdepth's form, e.g. 0:1:4:100: (classes 0:1, 1:4, 4:100, "
                    "100:inf); the value column is the class label, runs merge per class")
 @click.option('--zero/--no-zero', default=True,
               help="Write zero-depth runs (default; with --quantize: runs of the first class)")
-@click.option('--device', type=int, default=0, help="HIP device ordinal")
-@click.option('--decode', type=click.Choice(['gpu', 'host']), default='gpu',
-              help="gpu (default): BGZF inflate and record parse on the device; "
-                   "host: the C++ decoder on host threads")
-@click.option('--legacy-endpos', is_flag=True, default=False,
-              help="Count a mapped read without reference-consuming CIGAR ops on one column "
-                   "(htslib <= 1.9 bam_endpos); default: it adds nothing (current htslib)")
+@_opt_engine
 def depth(bamfile, outfile, regionfile_blast7, regionfile_csv, quantize, zero, device, decode,
           legacy_endpos):
     """
@@ -618,29 +698,19 @@ def depth(bamfile, outfile, regionfile_blast7, regionfile_csv, quantize, zero, d
     applied here.  Single process only.
     """
     from . import runs as _runs
-    if regionfile_blast7 and regionfile_csv:
-        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    _one_region_file(regionfile_blast7, regionfile_csv)
     if quantize:
         try:
             _runs.parse_quantize(quantize)
         except ValueError as e:
             raise click.BadParameter(str(e), param_hint="--quantize")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("depth runs in one process (WORLD_SIZE > 1 is not supported: "
-                               "its output is not sharded)")
+    _single_process("depth")
     if decode == 'gpu':
         bam = GpuBamFile(bamfile.name, device=device, legacy_endpos=legacy_endpos)
     else:
         bam = BamFile(bamfile.name, legacy_endpos=legacy_endpos)
     log_counts(bam)
-    err = None
-    if regionfile_blast7 or regionfile_csv:
-        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, bam)
-        _, tids, starts, ends, err = resolve_regions(bam, regions)
-    else:
-        tids = np.arange(len(bam.lengths), dtype=np.int32)
-        starts = np.zeros(len(tids), np.int64)
-        ends = np.asarray(bam.lengths, np.int64)
+    tids, starts, ends, err, _ = _select_segments(bam, regionfile_blast7, regionfile_csv)
     n = write_depth(bam, tids, starts, ends, outfile, device=device, quantize=quantize, zero=zero)
     outfile.flush()
     log.info("%d runs written", n)
@@ -658,7 +728,7 @@ def write_coverage(bam, tids, starts, ends, outfile, device=0, by=0, thresholds=
     cumulative depth distribution per segment (labels) and in total."""
     from . import windows as _windows
     thr = _windows.parse_thresholds(thresholds) if thresholds else []
-    names = [w.split()[0] if w.split() else w for w in bam.references]
+    names = _bases.contig_names(bam.references)
     if len(tids) == 0:
         _windows.write_windows_bed(_windows.WindowCoverage([], [], [], by, thr, [0], [], []), names, outfile)
         if dist is not None:
@@ -687,12 +757,8 @@ def write_coverage(bam, tids, starts, ends, outfile, device=0, by=0, thresholds=
               help="Input BAM file. Must be coordinate-sorted.")
 @click.option('--outfile', '-o', type=click.File('w'), default="-",
               help="Output windows table (default STDOUT)")
-@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
-              help="Input Region file in BLAST7 format")
-@click.option('--regionfile-csv', '-rc', type=click.File('r'),
-              help="Input Region file in CSV format")
-@click.option('--by', type=int, default=0, metavar="N",
-              help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
+@_opt_regions
+@_opt_by
 @click.option('--thresholds', metavar="LIST",
               help="Depths, e.g. 1,10,30: one more column each, the positions at or above it")
 @click.option('--dist', type=click.File('w'), metavar="FILE",
@@ -700,13 +766,7 @@ def write_coverage(bam, tids, starts, ends, outfile, device=0, by=0, thresholds=
                    "(or per region, labelled name:start-end), then in total")
 @click.option('--dist-bins', type=int, default=1024, metavar="N",
               help="Bins of --dist (default 1024); the last one holds every depth at or above N - 1")
-@click.option('--device', type=int, default=0, help="HIP device ordinal")
-@click.option('--decode', type=click.Choice(['gpu', 'host']), default='gpu',
-              help="gpu (default): BGZF inflate and record parse on the device; "
-                   "host: the C++ decoder on host threads")
-@click.option('--legacy-endpos', is_flag=True, default=False,
-              help="Count a mapped read without reference-consuming CIGAR ops on one column "
-                   "(htslib <= 1.9 bam_endpos); default: it adds nothing (current htslib)")
+@_opt_engine
 def coverage(bamfile, outfile, regionfile_blast7, regionfile_csv, by, thresholds, dist, dist_bins, device,
              decode, legacy_endpos):
     """
@@ -721,8 +781,7 @@ def coverage(bamfile, outfile, regionfile_blast7, regionfile_csv, by, thresholds
     per region query is not applied here.  Single process only.
     """
     from . import windows as _windows
-    if regionfile_blast7 and regionfile_csv:
-        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
+    _one_region_file(regionfile_blast7, regionfile_csv)
     if by != 0 and by < _windows.MIN_WINDOW:
         raise click.BadParameter("must be 0 or at least %d (for shorter windows write `depth` runs)"
                                  % _windows.MIN_WINDOW, param_hint="--by")
@@ -733,9 +792,7 @@ def coverage(bamfile, outfile, regionfile_blast7, regionfile_csv, by, thresholds
             raise click.BadParameter(str(e), param_hint="--thresholds")
     if dist_bins < 1:
         raise click.BadParameter("must be at least 1", param_hint="--dist-bins")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("coverage runs in one process (WORLD_SIZE > 1 is not supported: "
-                               "its output is not sharded)")
+    _single_process("coverage")
     if decode == 'gpu':
         bam = GpuBamFile(bamfile.name, device=device, legacy_endpos=legacy_endpos)
     else:
@@ -743,17 +800,10 @@ def coverage(bamfile, outfile, regionfile_blast7, regionfile_csv, by, thresholds
     log_counts(bam)
     if dist is not None and dist_bins > _windows.dims()[2]:
         raise click.BadParameter("at most %d" % _windows.dims()[2], param_hint="--dist-bins")
-    err = None
-    names = [w.split()[0] if w.split() else w for w in bam.references]
-    if regionfile_blast7 or regionfile_csv:
-        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, bam)
-        _, tids, starts, ends, err = resolve_regions(bam, regions)
+    labels = names = _bases.contig_names(bam.references)
+    tids, starts, ends, err, from_regions = _select_segments(bam, regionfile_blast7, regionfile_csv)
+    if from_regions:
         labels = ["%s:%d-%d" % (names[int(t)], a, b) for t, a, b in zip(tids, starts, ends)]
-    else:
-        tids = np.arange(len(bam.lengths), dtype=np.int32)
-        starts = np.zeros(len(tids), np.int64)
-        ends = np.asarray(bam.lengths, np.int64)
-        labels = names
     n = write_coverage(bam, tids, starts, ends, outfile, device=device, by=by, thresholds=thresholds,
                        dist=dist, dist_bins=dist_bins, labels=labels)
     outfile.flush()
@@ -780,6 +830,50 @@ def _segment_letters(fa, name, start, end):
     return out
 
 
+def _group_passes(paths, references, tids, starts, ends, counts, limit, device=0, decode="host", min_baseq=0,
+                  min_mapq=0, fasta=None, **tracking):
+    """The pass over the segments (header contig ids) that write_bases,
+    write_consensus, write_diversity and write_compare share: a generator of
+    (a, b, counters, letters) per group [a, b) of at most `limit` positions,
+    the group before it done with.  counters: one BaseCounter per path, begun
+    on the group's segments (tracking: begin's flags) and filled with the
+    path's reads; decode "host": one pass over the file on host threads per
+    group, "gpu": the file is decoded once on the device and every group
+    reads the resident records.  letters: with `fasta` the group's reference
+    letters, uint8 ASCII indexed like a plane, else None.  counts [len(paths)]
+    receives the sources' record counts.  Closing the generator closes the
+    counters and the sources."""
+    if len(tids) == 0:
+        return
+    names = _bases.contig_names(references)
+    fa = _experimental.FastaFile(fasta) if fasta else None
+    with contextlib.ExitStack() as stack:
+        bcs = [stack.enter_context(_bases.BaseCounter(len(references), device)) for _ in paths]
+        srcs = [None] * len(paths)
+        if decode == "gpu":
+            for k, path in enumerate(paths):
+                try:
+                    srcs[k] = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
+                except _bases._lib.MetacovError as e:
+                    if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
+                        raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
+                                                   "run with --decode host (%s)" % (path, device, e))
+                    raise
+        for a, b in depth_groups(starts, ends, limit):
+            for k, path in enumerate(paths):
+                bcs[k].begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, **tracking)
+                if srcs[k] is not None:
+                    bcs[k].add_device(srcs[k])
+                    counts[k] = srcs[k].counts()
+                else:
+                    counts[k] = bcs[k].add_bam(path, min_mapq=min_mapq)
+            letters = None
+            if fa is not None:
+                letters = np.concatenate([_segment_letters(fa, names[int(tids[i])], starts[i], ends[i])
+                                          for i in range(a, b)] + [np.zeros(0, np.uint8)])
+            yield a, b, bcs, letters
+
+
 def write_bases(path, references, tids, starts, ends, outfile, fasta=None, device=0, min_baseq=0, min_mapq=0,
                 min_depth=1, min_count=1, min_ppm=0, every=False, decode="host", insertions=None, strand=False,
                 min_alt_strand=0, quality=False, min_alt_baseq=0, min_alt_mapq=0):
@@ -796,9 +890,7 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
     then also needs an alternative allele whose sums reach min_alt_baseq and
     min_alt_mapq times its count.  Returns (lines written, the source's record
     counts)."""
-    from . import bases as _bases
-    import contextlib
-    names = [w.split()[0] if w.split() else w for w in references]
+    names = _bases.contig_names(references)
     if min_alt_strand and not strand:
         raise ValueError("min_alt_strand needs strand")
     if (min_alt_baseq or min_alt_mapq) and not quality:
@@ -808,37 +900,15 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
     outfile.write(_bases.HEADER_STRAND if strand else _bases.HEADER_QUALITY if quality else _bases.HEADER)
     if insertions is not None:
         insertions.write(_bases.INSERTIONS_HEADER)
-    written, counts = 0, None
-    if len(tids) == 0:
-        return 0, None
-    fa = _experimental.FastaFile(fasta) if fasta else None
-    with contextlib.ExitStack() as stack:
-        bc = stack.enter_context(_bases.BaseCounter(len(references), device))
-        src = None
-        if decode == "gpu":
-            try:
-                src = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
-            except _bases._lib.MetacovError as e:
-                if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
-                    raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
-                                               "run with --decode host (%s)" % (path, device, e))
-                raise
-        for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
-            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions is not None,
-                     strand=strand, quality=quality)
-            if src is not None:
-                bc.add_device(src)
-                counts = src.counts()
-            else:
-                counts = bc.add_bam(path, min_mapq=min_mapq)
+    written, counts = 0, [None]
+    with contextlib.closing(_group_passes(
+            [path], references, tids, starts, ends, counts, BASES_GROUP_POSITIONS, device, decode, min_baseq, min_mapq,
+            fasta, insertions=insertions is not None, strand=strand, quality=quality)) as groups:
+        for a, b, (bc,), letters in groups:
             seg_off = bc.seg_off
             if insertions is not None:
                 _write_insertions(bc, names, tids[a:b], starts[a:b], seg_off, min_depth, min_count, min_ppm,
                                   insertions)
-            letters = None
-            if fa is not None:
-                letters = np.concatenate([_segment_letters(fa, names[int(tids[i])], starts[i], ends[i])
-                                          for i in range(a, b)] + [np.zeros(0, np.uint8)])
             if every:
                 for i in range(a, b):
                     o, n = int(seg_off[i - a]), int(ends[i] - starts[i])
@@ -864,14 +934,13 @@ def write_bases(path, references, tids, starts, ends, outfile, fasta=None, devic
                                                   rev=s.rev_counts[r0:r1] if strand else None,
                                                   bq=s.bq_sums[r0:r1] if quality else None,
                                                   mq=s.mq_sums[r0:r1] if quality else None)
-    return written, counts
+    return written, counts[0]
 
 
 def _write_insertions(bc, names, tids, starts, seg_off, min_depth, min_count, min_ppm, fh):
     """The insertion rows of the counter's current segments, in segment and
     position order; the depth column from the planes, fetched over the span of
     at most GET_CHUNK positions that a run of rows covers.  Returns the lines."""
-    from . import bases as _bases
     ins = bc.insertions(min_depth, min_count, min_ppm)
     written = 0
     for i in range(len(tids)):
@@ -902,14 +971,8 @@ def _write_insertions(bc, names, tids, starts, seg_off, min_depth, min_count, mi
               help="Also write the insertion alleles `contig pos depth count len seq` (pos: the base before "
                    "the inserted ones; seq `*`: longer than 32 or with an ambiguity code) that pass "
                    "--min-depth, --min-count and --min-frac with their own count")
-@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
-              help="Input Region file in BLAST7 format")
-@click.option('--regionfile-csv', '-rc', type=click.File('r'),
-              help="Input Region file in CSV format")
-@click.option('--min-baseq', type=click.IntRange(0), default=0,
-              help="Count only bases of at least this quality (deletions always count)")
-@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
-              help="Use only reads of at least this mapping quality")
+@_opt_regions
+@_opt_floors("Count only bases of at least this quality (deletions always count)")
 @click.option('--min-depth', type=click.IntRange(0), default=1,
               help="A site needs A + C + G + T + DEL of at least this")
 @click.option('--min-count', type=click.IntRange(0), default=1,
@@ -933,10 +996,7 @@ def _write_insertions(bc, names, tids, starts, seg_off, min_depth, min_count, mi
                    "whose mean base quality is at least this (a deletion is exempt; needs --quality)")
 @click.option('--min-alt-mapq', type=click.IntRange(0, 255), default=0,
               help="... and whose reads' mean MAPQ is at least this (needs --quality)")
-@click.option('--device', type=int, default=0, help="HIP device ordinal")
-@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
-              help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
-                   "the GPU, the records staying in device memory (the file's reads must fit there)")
+@_opt_counter()
 def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regionfile_csv, min_baseq, min_mapq,
           min_depth, min_count, min_frac, every, strand, min_alt_strand, quality, min_alt_baseq, min_alt_mapq, device,
           decode):
@@ -955,12 +1015,8 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     contig in header order, or the regions of a region file in file order.
     Counted on the GPU; single process only.
     """
-    from . import bases as _bases
-    if regionfile_blast7 and regionfile_csv:
-        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
-    if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
-        raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
-    min_ppm = int(round(min_frac * 1e6))
+    _one_region_file(regionfile_blast7, regionfile_csv)
+    min_ppm = _ppm(min_frac, "--min-frac")
     if min_alt_strand and not strand:
         raise click.UsageError("--min-alt-strand needs --strand")
     if min_alt_baseq and not quality:
@@ -969,22 +1025,13 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
         raise click.UsageError("--min-alt-mapq needs --quality")
     if quality and strand:
         raise click.UsageError("--quality and --strand cannot be combined")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("bases runs in one process (WORLD_SIZE > 1 is not supported: "
-                               "its output is not sharded)")
+    _single_process("bases")
     # (read by experimental.FastaFile as `pileup -f -k` and `scan -f` read theirs: plain or gzip.  `pileup`
     # also fails where pysam's faidx would, to match the reference; `bases` has no reference to match)
     fasta = reference_fasta.name if reference_fasta else None
     with _bases.BaseSource(bamfile.name) as head:
-        references, lengths = list(head.references), list(head.lengths)
-    err = None
-    if regionfile_blast7 or regionfile_csv:
-        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
-        _, tids, starts, ends, err = resolve_regions(head, regions)
-    else:
-        tids = np.arange(len(lengths), dtype=np.int32)
-        starts = np.zeros(len(tids), np.int64)
-        ends = np.asarray(lengths, np.int64)
+        references = list(head.references)
+    tids, starts, ends, err, _ = _select_segments(head, regionfile_blast7, regionfile_csv)
     n, counts = write_bases(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
                             min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth, min_count=min_count,
                             min_ppm=min_ppm, every=every, decode=decode, insertions=insertions, strand=strand,
@@ -993,9 +1040,7 @@ def bases(bamfile, outfile, reference_fasta, insertions, regionfile_blast7, regi
     outfile.flush()
     if insertions is not None:
         insertions.flush()
-    if counts:
-        log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
-                 "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    _log_record_counts(counts)
     log.info("%d lines written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err
@@ -1010,48 +1055,25 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
     called insertion alleles are part of the letters (not with aligned) and
     the table has two more columns.  Returns (records written, the source's
     record counts)."""
-    from . import bases as _bases
-    import contextlib
     if insertions and aligned:
         raise ValueError("insertions has no place in the aligned output")
-    names = [w.split()[0] if w.split() else w for w in references]
+    names = _bases.contig_names(references)
     if summary is not None:
         summary.write(_bases.SUMMARY_HEADER_INS if insertions else _bases.SUMMARY_HEADER)
-    counts = None
-    if len(tids) == 0:
-        return 0, None
-    fa = _experimental.FastaFile(fasta) if fasta else None
-    with contextlib.ExitStack() as stack:
-        bc = stack.enter_context(_bases.BaseCounter(len(references), device))
-        src = None
-        if decode == "gpu":
-            try:
-                src = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
-            except _bases._lib.MetacovError as e:
-                if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
-                    raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
-                                               "run with --decode host (%s)" % (path, device, e))
-                raise
-        for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
-            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq, insertions=insertions)
-            if src is not None:
-                bc.add_device(src)
-                counts = src.counts()
-            else:
-                counts = bc.add_bam(path, min_mapq=min_mapq)
-            codes = None
-            if fa is not None:
-                codes = _bases.ref_codes(np.concatenate(
-                    [_segment_letters(fa, names[int(tids[i])], starts[i], ends[i]) for i in range(a, b)] +
-                    [np.zeros(0, np.uint8)]))
-            cons = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref, codes, insertions=insertions)
+    counts = [None]
+    with contextlib.closing(_group_passes(
+            [path], references, tids, starts, ends, counts, BASES_GROUP_POSITIONS, device, decode, min_baseq, min_mapq,
+            fasta, insertions=insertions)) as groups:
+        for a, b, (bc,), letters in groups:
+            cons = bc.consensus(min_depth, min_count, call_ppm, iupac, fill_ref,
+                                None if letters is None else _bases.ref_codes(letters), insertions=insertions)
             for i in range(a, b):
                 _bases.write_fasta(outfile, labels[i], cons.aligned(i - a) if aligned else cons.compact(i - a),
                                    line_width)
             if summary is not None:
                 _bases.write_consensus_summary(summary, [names[int(t)] for t in tids[a:b]], starts[a:b], ends[a:b],
                                                cons.summary, header=False, inserted=cons.inserted)
-    return len(tids), counts
+    return len(tids), counts[0]
 
 
 @main.command()
@@ -1061,14 +1083,8 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
               help="Output FASTA (default STDOUT)")
 @click.option('--reference-fasta', '-f', type=click.File('rb'),
               help="Reference FASTA (plain or gzip): counts the differences for --summary and serves --fill-ref")
-@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
-              help="Input Region file in BLAST7 format")
-@click.option('--regionfile-csv', '-rc', type=click.File('r'),
-              help="Input Region file in CSV format")
-@click.option('--min-baseq', type=click.IntRange(0), default=0,
-              help="Count only bases of at least this quality (deletions always count)")
-@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
-              help="Use only reads of at least this mapping quality")
+@_opt_regions
+@_opt_floors("Count only bases of at least this quality (deletions always count)")
 @click.option('--min-depth', type=click.IntRange(0), default=1, show_default=True,
               help="Below this A + C + G + T + DEL a position is N (or the reference base with --fill-ref)")
 @click.option('--min-count', type=click.IntRange(0), default=1, show_default=True,
@@ -1089,10 +1105,7 @@ def write_consensus(path, references, tids, starts, ends, labels, outfile, fasta
                    "per record (with --insertions two more columns: insertions, inserted)")
 @click.option('--line-width', type=click.IntRange(0), default=60, show_default=True,
               help="Letters per FASTA line; 0: no wrap")
-@click.option('--device', type=int, default=0, help="HIP device ordinal")
-@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
-              help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
-                   "the GPU, the records staying in device memory (the file's reads must fit there)")
+@_opt_counter()
 def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_csv, min_baseq, min_mapq, min_depth,
               min_count, call_frac, iupac, fill_ref, aligned, insertions, summary, line_width, device, decode):
     """
@@ -1108,34 +1121,21 @@ def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_c
     thresholds, follows that position's letter.  Called on the GPU; single
     process only.
     """
-    from . import bases as _bases
-    if regionfile_blast7 and regionfile_csv:
-        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
-    if not 0.0 <= call_frac <= 1.0:         # (nan fails both comparisons)
-        raise click.BadParameter("must lie in [0, 1]", param_hint="--call-frac")
+    _one_region_file(regionfile_blast7, regionfile_csv)
+    call_ppm = _ppm(call_frac, "--call-frac")
     if fill_ref and not reference_fasta:
         raise click.BadParameter("needs a reference (-f)", param_hint="--fill-ref")
     if insertions and aligned:
         raise click.BadParameter("the aligned output has one letter per reference position and no place for "
                                  "inserted bases", param_hint="--insertions")
-    call_ppm = int(round(call_frac * 1e6))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("consensus runs in one process (WORLD_SIZE > 1 is not supported: "
-                               "its output is not sharded)")
+    _single_process("consensus")
     fasta = reference_fasta.name if reference_fasta else None
     with _bases.BaseSource(bamfile.name) as head:
-        references, lengths = list(head.references), list(head.lengths)
-    names = [w.split()[0] if w.split() else w for w in references]
-    err = None
-    if regionfile_blast7 or regionfile_csv:
-        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
-        _, tids, starts, ends, err = resolve_regions(head, regions)
+        references = list(head.references)
+    labels = names = _bases.contig_names(references)
+    tids, starts, ends, err, from_regions = _select_segments(head, regionfile_blast7, regionfile_csv)
+    if from_regions:
         labels = ["%s:%d-%d" % (names[int(t)], a + 1, b) for t, a, b in zip(tids, starts, ends)]
-    else:
-        tids = np.arange(len(lengths), dtype=np.int32)
-        starts = np.zeros(len(tids), np.int64)
-        ends = np.asarray(lengths, np.int64)
-        labels = names
     n, counts = write_consensus(bamfile.name, references, tids, starts, ends, labels, outfile, fasta=fasta,
                                 device=device, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
                                 min_count=min_count, call_ppm=call_ppm, iupac=iupac, fill_ref=fill_ref,
@@ -1144,9 +1144,7 @@ def consensus(bamfile, outfile, reference_fasta, regionfile_blast7, regionfile_c
     outfile.flush()
     if summary is not None:
         summary.flush()
-    if counts:
-        log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
-                 "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    _log_record_counts(counts)
     log.info("%d sequences written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err
@@ -1158,41 +1156,18 @@ def write_diversity(path, references, tids, starts, ends, outfile, fasta=None, d
     as write_bases does it, each written before the next is computed: one line
     per segment, or per window of `by` positions.  Returns (lines written, the
     source's record counts)."""
-    from . import bases as _bases
-    import contextlib
-    names = [w.split()[0] if w.split() else w for w in references]
+    names = _bases.contig_names(references)
     outfile.write(_bases.DIVERSITY_HEADER)
-    written, counts = 0, None
-    if len(tids) == 0:
-        return 0, None
-    fa = _experimental.FastaFile(fasta) if fasta else None
-    with contextlib.ExitStack() as stack:
-        bc = stack.enter_context(_bases.BaseCounter(len(references), device))
-        src = None
-        if decode == "gpu":
-            try:
-                src = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
-            except _bases._lib.MetacovError as e:
-                if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
-                    raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
-                                               "run with --decode host (%s)" % (path, device, e))
-                raise
-        for a, b in depth_groups(starts, ends, BASES_GROUP_POSITIONS):
-            bc.begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
-            if src is not None:
-                bc.add_device(src)
-                counts = src.counts()
-            else:
-                counts = bc.add_bam(path, min_mapq=min_mapq)
-            codes = None
-            if fa is not None:
-                codes = _bases.ref_codes(np.concatenate(
-                    [_segment_letters(fa, names[int(tids[i])], starts[i], ends[i]) for i in range(a, b)] +
-                    [np.zeros(0, np.uint8)]))
-            div = bc.diversity(by, min_depth, min_count, min_ppm, codes)
+    written, counts = 0, [None]
+    with contextlib.closing(_group_passes(
+            [path], references, tids, starts, ends, counts, BASES_GROUP_POSITIONS, device, decode, min_baseq, min_mapq,
+            fasta)) as groups:
+        for a, b, (bc,), letters in groups:
+            div = bc.diversity(by, min_depth, min_count, min_ppm,
+                               None if letters is None else _bases.ref_codes(letters))
             written += _bases.write_diversity(outfile, [names[int(t)] for t in tids[a:b]], starts[a:b], div,
                                               header=False)
-    return written, counts
+    return written, counts[0]
 
 
 @main.command()
@@ -1200,28 +1175,18 @@ def write_diversity(path, references, tids, starts, ends, outfile, fasta=None, d
               help="Input BAM file. Must be coordinate-sorted.")
 @click.option('--outfile', '-o', type=click.File('w'), default="-",
               help="Output table (default STDOUT)")
-@click.option('--by', type=int, default=0, metavar="N",
-              help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
+@_opt_by
 @click.option('--reference-fasta', '-f', type=click.File('rb'),
               help="Reference FASTA (plain or gzip): fills compared, con_diff, pop_diff and the two identities")
-@click.option('--min-baseq', type=click.IntRange(0), default=0,
-              help="Count only bases of at least this quality")
-@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
-              help="Use only reads of at least this mapping quality")
+@_opt_floors("Count only bases of at least this quality")
 @click.option('--min-depth', type=click.IntRange(0), default=5, show_default=True,
               help="A position is covered with A + C + G + T of at least this (never below 2)")
 @click.option('--min-count', type=click.IntRange(0), default=2, show_default=True,
               help="An allele is present in the population with this many reads ...")
 @click.option('--min-frac', type=float, default=0.05, show_default=True,
               help="... and this fraction (0..1) of the position's bases")
-@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
-              help="Input Region file in BLAST7 format")
-@click.option('--regionfile-csv', '-rc', type=click.File('r'),
-              help="Input Region file in CSV format")
-@click.option('--device', type=int, default=0, help="HIP device ordinal")
-@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
-              help="Where the BAM is decoded: on host threads, one pass per group of 2^30 positions, or once on "
-                   "the GPU, the records staying in device memory (the file's reads must fit there)")
+@_opt_regions
+@_opt_counter()
 def diversity(bamfile, outfile, by, reference_fasta, min_baseq, min_mapq, min_depth, min_count, min_frac,
               regionfile_blast7, regionfile_csv, device, decode):
     """
@@ -1238,35 +1203,19 @@ def diversity(bamfile, outfile, by, reference_fasta, min_baseq, min_mapq, min_de
     major allele or passes the two thresholds; without it both are NA.
     Deletions are not bases here.  Reduced on the GPU; single process only.
     """
-    from . import bases as _bases
-    if regionfile_blast7 and regionfile_csv:
-        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
-    if by != 0 and by < _bases.DIV_MIN_WINDOW:
-        raise click.BadParameter("must be 0 or at least %d" % _bases.DIV_MIN_WINDOW, param_hint="--by")
-    if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
-        raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
-    min_ppm = int(round(min_frac * 1e6))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("diversity runs in one process (WORLD_SIZE > 1 is not supported: "
-                               "its output is not sharded)")
+    _one_region_file(regionfile_blast7, regionfile_csv)
+    _window_at_least(by)
+    min_ppm = _ppm(min_frac, "--min-frac")
+    _single_process("diversity")
     fasta = reference_fasta.name if reference_fasta else None
     with _bases.BaseSource(bamfile.name) as head:
-        references, lengths = list(head.references), list(head.lengths)
-    err = None
-    if regionfile_blast7 or regionfile_csv:
-        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
-        _, tids, starts, ends, err = resolve_regions(head, regions)
-    else:
-        tids = np.arange(len(lengths), dtype=np.int32)
-        starts = np.zeros(len(tids), np.int64)
-        ends = np.asarray(lengths, np.int64)
+        references = list(head.references)
+    tids, starts, ends, err, _ = _select_segments(head, regionfile_blast7, regionfile_csv)
     n, counts = write_diversity(bamfile.name, references, tids, starts, ends, outfile, fasta=fasta, device=device,
                                 by=by, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
                                 min_count=min_count, min_ppm=min_ppm, decode=decode)
     outfile.flush()
-    if counts:
-        log.info("Number of records:\n  total:    {records}\n  kept:     {kept}\n"
-                 "  skipped, no SEQ:           {no_seq}\n  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(**counts))
+    _log_record_counts(counts)
     log.info("%d windows written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err
@@ -1283,33 +1232,13 @@ def write_compare(path_a, path_b, references, tids, starts, ends, outfile, devic
     group by group as write_diversity does it, each written before the next is
     computed: one line per segment, or per window of `by` positions.  Returns
     (lines written, the record counts of the two sources)."""
-    from . import bases as _bases
-    import contextlib
-    names = [w.split()[0] if w.split() else w for w in references]
+    names = _bases.contig_names(references)
     outfile.write(_bases.COMPARE_HEADER)
     written, counts = 0, [None, None]
-    if len(tids) == 0:
-        return 0, counts
-    with contextlib.ExitStack() as stack:
-        bcs = [stack.enter_context(_bases.BaseCounter(len(references), device)) for _ in range(2)]
-        srcs = [None, None]
-        if decode == "gpu":
-            for k, path in enumerate((path_a, path_b)):
-                try:
-                    srcs[k] = stack.enter_context(_bases.GpuBaseSource(path, device, min_mapq=min_mapq))
-                except _bases._lib.MetacovError as e:
-                    if "do not fit in device memory" in str(e) or "out of memory" in str(e).lower():
-                        raise click.ClickException("%s: the decoded reads do not fit in the memory of device %d; "
-                                                   "run with --decode host (%s)" % (path, device, e))
-                    raise
-        for a, b in depth_groups(starts, ends, COMPARE_GROUP_POSITIONS):
-            for k, path in enumerate((path_a, path_b)):
-                bcs[k].begin(tids[a:b], starts[a:b], ends[a:b], min_baseq=min_baseq)
-                if srcs[k] is not None:
-                    bcs[k].add_device(srcs[k])
-                    counts[k] = srcs[k].counts()
-                else:
-                    counts[k] = bcs[k].add_bam(path, min_mapq=min_mapq)
+    with contextlib.closing(_group_passes(
+            [path_a, path_b], references, tids, starts, ends, counts, COMPARE_GROUP_POSITIONS, device, decode,
+            min_baseq, min_mapq)) as groups:
+        for a, b, bcs, _ in groups:
             cmp = bcs[0].compare(bcs[1], by, min_depth, min_count, min_ppm)
             written += _bases.write_compare(outfile, [names[int(t)] for t in tids[a:b]], starts[a:b], cmp,
                                             header=False)
@@ -1323,26 +1252,17 @@ def write_compare(path_a, path_b, references, tids, starts, ends, outfile, devic
               help="Sample B: a BAM file with the same reference names and lengths in the same order.")
 @click.option('--outfile', '-o', type=click.File('w'), default="-",
               help="Output table (default STDOUT)")
-@click.option('--by', type=int, default=0, metavar="N",
-              help="0 (default): one row per contig / region; N >= 16: fixed windows of N positions")
-@click.option('--min-baseq', type=click.IntRange(0), default=0,
-              help="Count only bases of at least this quality")
-@click.option('--min-mapq', type=click.IntRange(0, 255), default=0,
-              help="Use only reads of at least this mapping quality")
+@_opt_by
+@_opt_floors("Count only bases of at least this quality")
 @click.option('--min-depth', type=click.IntRange(0), default=5, show_default=True,
               help="A position is covered in a sample with A + C + G + T of at least this (never below 2)")
 @click.option('--min-count', type=click.IntRange(0), default=2, show_default=True,
               help="An allele is present in a sample with this many reads ...")
 @click.option('--min-frac', type=float, default=0.05, show_default=True,
               help="... and this fraction (0..1) of that sample's bases at the position")
-@click.option('--regionfile-blast7', '-rb', type=click.File('r'),
-              help="Input Region file in BLAST7 format")
-@click.option('--regionfile-csv', '-rc', type=click.File('r'),
-              help="Input Region file in CSV format")
-@click.option('--device', type=int, default=0, help="HIP device ordinal")
-@click.option('--decode', type=click.Choice(['host', 'gpu']), default='host',
-              help="Where the BAMs are decoded: on host threads, one pass per group of 2^29 positions, or once each "
-                   "on the GPU, the records staying in device memory (both files' reads must fit there)")
+@_opt_regions
+@_opt_counter("Where the BAMs are decoded: on host threads, one pass per group of 2^29 positions, or once each "
+              "on the GPU, the records staying in device memory (both files' reads must fit there)")
 def compare(bamfile, compare_bamfile, outfile, by, min_baseq, min_mapq, min_depth, min_count, min_frac,
             regionfile_blast7, regionfile_csv, device, decode):
     """
@@ -1360,40 +1280,23 @@ def compare(bamfile, compare_bamfile, outfile, by, min_baseq, min_mapq, min_dept
     bases here.  Reduced on the GPU from both samples' counts; single process
     only.
     """
-    from . import bases as _bases
-    if regionfile_blast7 and regionfile_csv:
-        raise click.BadParameter("Only one of regionfile-blast7 and regionfile-csv may be specified")
-    if by != 0 and by < _bases.DIV_MIN_WINDOW:
-        raise click.BadParameter("must be 0 or at least %d" % _bases.DIV_MIN_WINDOW, param_hint="--by")
-    if not 0.0 <= min_frac <= 1.0:          # (nan fails both comparisons)
-        raise click.BadParameter("must lie in [0, 1]", param_hint="--min-frac")
-    min_ppm = int(round(min_frac * 1e6))
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise click.UsageError("compare runs in one process (WORLD_SIZE > 1 is not supported: "
-                               "its output is not sharded)")
+    _one_region_file(regionfile_blast7, regionfile_csv)
+    _window_at_least(by)
+    min_ppm = _ppm(min_frac, "--min-frac")
+    _single_process("compare")
     with _bases.BaseSource(bamfile.name) as head, _bases.BaseSource(compare_bamfile.name) as other:
-        references, lengths = list(head.references), list(head.lengths)
-        diff = _bases.same_references(bamfile.name, references, lengths, compare_bamfile.name,
+        references = list(head.references)
+        diff = _bases.same_references(bamfile.name, references, list(head.lengths), compare_bamfile.name,
                                       list(other.references), list(other.lengths))
     if diff:
         raise click.ClickException("the two files do not share one reference: " + diff)
-    err = None
-    if regionfile_blast7 or regionfile_csv:
-        regions = _regions.make_region_iterator(regionfile_blast7, regionfile_csv, head)
-        _, tids, starts, ends, err = resolve_regions(head, regions)
-    else:
-        tids = np.arange(len(lengths), dtype=np.int32)
-        starts = np.zeros(len(tids), np.int64)
-        ends = np.asarray(lengths, np.int64)
+    tids, starts, ends, err, _ = _select_segments(head, regionfile_blast7, regionfile_csv)
     n, counts = write_compare(bamfile.name, compare_bamfile.name, references, tids, starts, ends, outfile,
                               device=device, by=by, min_baseq=min_baseq, min_mapq=min_mapq, min_depth=min_depth,
                               min_count=min_count, min_ppm=min_ppm, decode=decode)
     outfile.flush()
     for label, c in zip(("A", "B"), counts):
-        if c:
-            log.info("Sample {label}, number of records:\n  total:    {records}\n  kept:     {kept}\n"
-                     "  skipped, no SEQ:           {no_seq}\n"
-                     "  skipped, CIGAR != l_seq:   {bad_cigar}\n".format(label=label, **c))
+        _log_record_counts(c, label)
     log.info("%d windows written", n)
     if err is not None:      # the regions before a failing one are written first, as pileup does
         raise err

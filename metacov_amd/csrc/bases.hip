@@ -822,6 +822,26 @@ enum {
     kEvents
 };
 
+// The per-window rows of one stage (mc_bases_diversity, mc_bases_compare) and what tells the two apart: the pin
+// slot of the bad word, the three timing events, the names in the state error and the tail of the range error.
+struct WindowRows {
+    int slot, ev_zero, ev_tile, ev_end;
+    const char *noun, *call, *bad_what;
+    bool have = false;
+    int64_t n = 0;                       // windows in all
+    std::vector<int64_t> first;          // [S + 1]
+    Buf<DivTile> tiles;                  // [T]
+    Buf<int64_t> rows;                   // [n][8]
+    Buf<unsigned long long> bad;         // the lowest plane index with 2^26 bases or more (pin[slot] on the host)
+    float ms_tile = 0, ms_zero = 0;
+    void drop() {
+        have = false;
+        ms_tile = ms_zero = 0;
+    }
+};
+
+#define MC_REQUIRE_ROWS(r) MC_REQUIRE((r).have, MC_E_STATE, "no %s computed (call %s)", (r).noun, (r).call)
+
 }  // namespace
 
 // pin: [0] lowest bad read, [1] max span (int32), [2] site total, [3] consensus total, [4] insertion totals,
@@ -865,22 +885,12 @@ struct mc_bases : mc::StageHandle<kEvents, 9> {
     Buf<int32_t> cons_cols;              // [8][T]
     Buf<int64_t> cons_pre, cons_first, cons_rows;   // [8][T + 1], [S + 1], [S][8]
     float ms_cons_call = 0, ms_cons_scan = 0, ms_cons_emit = 0;
-    // diversity: buffers of its own again, so its rows live beside sites and a consensus
-    bool have_div = false;
-    int64_t n_div = 0;                   // windows in all
-    std::vector<int64_t> div_first;      // [S + 1]
-    Buf<DivTile> div_tiles;              // [T]
-    Buf<int64_t> div_rows;               // [n_div][8]
-    Buf<unsigned long long> div_bad;     // the lowest covered plane index with 2^26 bases or more (pin[7] on the host)
-    float ms_div_tile = 0, ms_div_zero = 0;
-    // comparison with another handle: buffers of its own once more
-    bool have_cmp = false;
-    int64_t n_cmp = 0;                   // windows in all
-    std::vector<int64_t> cmp_first;      // [S + 1]
-    Buf<DivTile> cmp_tiles;              // [T]
-    Buf<int64_t> cmp_rows;               // [n_cmp][8]
-    Buf<unsigned long long> cmp_bad;     // the lowest compared plane index with 2^26 bases or more (pin[8] on the host)
-    float ms_cmp_tile = 0, ms_cmp_zero = 0;
+    // diversity, and the comparison with another handle: buffers of their own again, so their rows live beside
+    // sites and a consensus and beside each other
+    WindowRows div{7, kEvDivZero, kEvDivTile, kEvDivEnd, "diversity", "mc_bases_diversity",
+                   "a covered position is 2^26 or more (pi_fix is exact below that)"};
+    WindowRows cmp{8, kEvCmpZero, kEvCmpTile, kEvCmpEnd, "comparison", "mc_bases_compare",
+                   "a compared position is 2^26 or more in one of the samples (dist_fix is exact below that)"};
     // insertions (opt-in, mc_bases_track_insertions): events, their sorted buckets, two row tables
     bool track_next = false, tracking = false;
     bool ins_from_set = false;           // mc_bases_ins_set installed the sorted buckets
@@ -951,12 +961,17 @@ void invalidate_ins(mc_bases* h) {
     h->have_cons_ins = false;
 }
 
+// The planes or the installed insertions changed: the window rows of both stages and their timings are gone.
+void drop_window_rows(mc_bases* h) {
+    h->div.drop();
+    h->cmp.drop();
+}
+
 // The planes changed: so are the sites, the consensus and the row tables (their rows were kept by depth).
 void invalidate_results(mc_bases* h) {
     h->have_sites = false;
     h->have_cons = false;
-    h->have_div = false;
-    h->have_cmp = false;
+    drop_window_rows(h);
     invalidate_ins(h);
 }
 
@@ -997,8 +1012,7 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->have_sites = false;
     h->have_cons = false;
     h->have_cons_ins = false;
-    h->have_div = false;
-    h->have_cmp = false;
+    drop_window_rows(h);
     h->tracking = false;
     h->strand = false;
     h->have_sites_rev = false;
@@ -1091,8 +1105,6 @@ extern "C" int mc_bases_begin(mc_bases* h, int64_t S, const int32_t* tid, const 
     h->n_reads = 0;
     h->ms_prepass = h->ms_pileup = h->ms_sites = 0;
     h->ms_cons_call = h->ms_cons_scan = h->ms_cons_emit = 0;
-    h->ms_div_tile = h->ms_div_zero = 0;
-    h->ms_cmp_tile = h->ms_cmp_zero = 0;
     h->begun = true;
     return MC_OK;
 }
@@ -2089,6 +2101,84 @@ DivArgs div_args(int64_t window, int64_t min_depth, int64_t min_count, int64_t m
                    window ? window : 2 * kMaxPos};
 }
 
+// One window-row result from h's planes, on h's stream: the windows, the bad word seeded, the DivTiles uploaded,
+// the rows tiles share zeroed, then the stage's tile kernel (`launch(stream)`, called only with tiles to run:
+// the one step that differs), the bad word back, the two times.  cols: the stage's columns per row.  The caller
+// has made h's device current and put what its kernel reads besides h's planes in front on the stream.
+template <typename Launch>
+int window_rows(mc_bases* h, WindowRows& r, int64_t window, const DivArgs& da, int cols, int64_t* n_windows,
+                Launch launch) {
+    r.have = false;
+    const int64_t T = h->n_tiles;
+    std::vector<int64_t> first;
+    std::vector<DivTile> dt;
+    int64_t nw = 0;
+    if (int rc = div_windows(h, window, first, dt, &nw)) return rc;
+    HIP_TRY(r.tiles.reserve((size_t)T));
+    HIP_TRY(r.rows.reserve((size_t)(nw * cols)));
+    HIP_TRY(r.bad.reserve(1));
+    hipStream_t st = h->stream;
+    h->pin[r.slot] = kNoBad;
+    HIP_TRY(hipMemcpyAsync(r.bad.p, h->pin + r.slot, 8, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(r.tiles.p, dt.data(), (size_t)T * sizeof(DivTile), hipMemcpyHostToDevice, st));
+    if (int rc = h->mark(r.ev_zero)) return rc;
+    if (T) {
+        hipLaunchKernelGGL(div_zero_kernel, dim3((unsigned)((T * 16 + 255) / 256)), dim3(256), 0, st, h->tiles.p,
+                           r.tiles.p, T, da.window, r.rows.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = h->mark(r.ev_tile)) return rc;
+    if (T) {
+        launch(st);
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = h->mark(r.ev_end)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->pin + r.slot, r.bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));            // (dt is released)
+    const unsigned long long bad = h->pin[r.slot];
+    MC_REQUIRE(bad == kNoBad, MC_E_RANGE, "plane index %llu: A + C + G + T of %s", bad, r.bad_what);
+    if (int rc = h->elapsed(r.ev_zero, r.ev_tile, &r.ms_zero)) return rc;
+    if (int rc = h->elapsed(r.ev_tile, r.ev_end, &r.ms_tile)) return rc;
+    r.first = std::move(first);
+    r.n = nw;
+    r.have = true;
+    *n_windows = nw;
+    return MC_OK;
+}
+
+// The four accessors of a window-row result (mc_bases_diversity_* and mc_bases_compare_*), behind the callers'
+// null checks.
+int rows_first(const WindowRows& r, int64_t* win_first) {
+    MC_REQUIRE_ROWS(r);
+    std::memcpy(win_first, r.first.data(), r.first.size() * 8);
+    return MC_OK;
+}
+
+int rows_get(const mc_bases* h, const WindowRows& r, int cols, int64_t first, int64_t count, int64_t* rows) {
+    MC_REQUIRE_ROWS(r);
+    if (int rc = check_range(first, count, r.n, "windows")) return rc;
+    MC_REQUIRE(count == 0 || rows, MC_E_INVALID, "null out");
+    if (count == 0) return MC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(rows, r.rows.p + first * cols, (size_t)count * cols * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return MC_OK;
+}
+
+int rows_device(const WindowRows& r, const int64_t** d_rows, int64_t* n_windows) {
+    MC_REQUIRE_ROWS(r);
+    *d_rows = r.rows.p;
+    *n_windows = r.n;
+    return MC_OK;
+}
+
+int rows_timing(const WindowRows& r, float* tile_ms, float* zero_ms) {
+    MC_REQUIRE_ROWS(r);
+    *tile_ms = r.ms_tile;
+    *zero_ms = r.ms_zero;
+    return MC_OK;
+}
+
 }  // namespace
 
 extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth, int64_t min_count, int64_t min_ppm,
@@ -2100,85 +2190,35 @@ extern "C" int mc_bases_diversity(mc_bases* h, int64_t window, int64_t min_depth
                (long long)min_depth, (long long)min_count, (long long)min_ppm);
     MC_REQUIRE(window == 0 || window >= MC_DIV_MIN_WINDOW, MC_E_INVALID, "window %lld: must be 0 or at least %d",
                (long long)window, MC_DIV_MIN_WINDOW);
-    h->have_div = false;
-    const int64_t T = h->n_tiles;
-    std::vector<int64_t> first;
-    std::vector<DivTile> dt;
-    int64_t nw = 0;
-    if (int rc = div_windows(h, window, first, dt, &nw)) return rc;
-    const DivArgs da = div_args(window, min_depth, min_count, min_ppm);
+    h->div.have = false;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(h->div_tiles.reserve((size_t)T));
-    HIP_TRY(h->div_rows.reserve((size_t)(nw * kDivCols)));
-    HIP_TRY(h->div_bad.reserve(1));
-    hipStream_t st = h->stream;
     const uint8_t* d_ref = nullptr;
     if (int rc = upload_ref(h, ref, &d_ref)) return rc;
-    h->pin[7] = kNoBad;
-    HIP_TRY(hipMemcpyAsync(h->div_bad.p, h->pin + 7, 8, hipMemcpyHostToDevice, st));
-    if (T) HIP_TRY(hipMemcpyAsync(h->div_tiles.p, dt.data(), (size_t)T * sizeof(DivTile), hipMemcpyHostToDevice, st));
-    if (int rc = h->mark(kEvDivZero)) return rc;
-    if (T) {
-        hipLaunchKernelGGL(div_zero_kernel, dim3((unsigned)((T * 16 + 255) / 256)), dim3(256), 0, st, h->tiles.p,
-                           h->div_tiles.p, T, da.window, h->div_rows.p);
-        HIP_TRY(hipGetLastError());
-    }
-    if (int rc = h->mark(kEvDivTile)) return rc;
-    if (T) {
-        hipLaunchKernelGGL(div_tile_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, h->planes.p, h->stride, d_ref,
-                           h->tiles.p, h->div_tiles.p, da, h->div_rows.p, h->div_bad.p);
-        HIP_TRY(hipGetLastError());
-    }
-    if (int rc = h->mark(kEvDivEnd)) return rc;
-    HIP_TRY(hipMemcpyAsync(h->pin + 7, h->div_bad.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));            // (dt is released)
-    const unsigned long long bad = h->pin[7];
-    MC_REQUIRE(bad == kNoBad, MC_E_RANGE,
-               "plane index %llu: A + C + G + T of a covered position is 2^26 or more (pi_fix is exact below that)",
-               bad);
-    if (int rc = h->elapsed(kEvDivZero, kEvDivTile, &h->ms_div_zero)) return rc;
-    if (int rc = h->elapsed(kEvDivTile, kEvDivEnd, &h->ms_div_tile)) return rc;
-    h->div_first = std::move(first);
-    h->n_div = nw;
-    h->have_div = true;
-    *n_windows = nw;
-    return MC_OK;
+    const DivArgs da = div_args(window, min_depth, min_count, min_ppm);
+    return window_rows(h, h->div, window, da, kDivCols, n_windows, [&](hipStream_t st) {
+        hipLaunchKernelGGL(div_tile_kernel, dim3((unsigned)h->n_tiles), dim3(kThreads), 0, st, h->planes.p, h->stride,
+                           d_ref, h->tiles.p, h->div.tiles.p, da, h->div.rows.p, h->div.bad.p);
+    });
 }
 
 extern "C" int mc_bases_diversity_first(const mc_bases* h, int64_t* win_first) {
     MC_REQUIRE(h && win_first, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
-    std::memcpy(win_first, h->div_first.data(), h->div_first.size() * 8);
-    return MC_OK;
+    return rows_first(h->div, win_first);
 }
 
 extern "C" int mc_bases_diversity_get(const mc_bases* h, int64_t first, int64_t count, int64_t* rows) {
     MC_REQUIRE(h, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
-    if (int rc = check_range(first, count, h->n_div, "windows")) return rc;
-    MC_REQUIRE(count == 0 || rows, MC_E_INVALID, "null out");
-    if (count == 0) return MC_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(rows, h->div_rows.p + first * kDivCols, (size_t)count * kDivCols * 8,
-                           hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return MC_OK;
+    return rows_get(h, h->div, kDivCols, first, count, rows);
 }
 
 extern "C" int mc_bases_diversity_device(const mc_bases* h, const int64_t** d_rows, int64_t* n_windows) {
     MC_REQUIRE(h && d_rows && n_windows, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
-    *d_rows = h->div_rows.p;
-    *n_windows = h->n_div;
-    return MC_OK;
+    return rows_device(h->div, d_rows, n_windows);
 }
 
 extern "C" int mc_bases_diversity_timing(const mc_bases* h, float* tile_ms, float* combine_ms) {
     MC_REQUIRE(h && tile_ms && combine_ms, MC_E_INVALID, "null argument");
-    MC_REQUIRE(h->have_div, MC_E_STATE, "no diversity computed (call mc_bases_diversity)");
-    *tile_ms = h->ms_div_tile;
-    *combine_ms = h->ms_div_zero;
-    return MC_OK;
+    return rows_timing(h->div, tile_ms, combine_ms);
 }
 
 // ---- comparison (the contract is the header's, "Comparison") ------------------
@@ -2204,88 +2244,37 @@ extern "C" int mc_bases_compare(mc_bases* a, const mc_bases* b, int64_t window, 
                (long long)min_depth, (long long)min_count, (long long)min_ppm);
     MC_REQUIRE(window == 0 || window >= MC_DIV_MIN_WINDOW, MC_E_INVALID, "window %lld: must be 0 or at least %d",
                (long long)window, MC_DIV_MIN_WINDOW);
-    a->have_cmp = false;
-    const int64_t T = a->n_tiles;
-    std::vector<int64_t> first;
-    std::vector<DivTile> dt;
-    int64_t nw = 0;
-    if (int rc = div_windows(a, window, first, dt, &nw)) return rc;
-    const DivArgs da = div_args(window, min_depth, min_count, min_ppm);
+    a->cmp.have = false;
     HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(a->cmp_tiles.reserve((size_t)T));
-    HIP_TRY(a->cmp_rows.reserve((size_t)(nw * kCmpCols)));
-    HIP_TRY(a->cmp_bad.reserve(1));
-    hipStream_t st = a->stream;
     if (a != b) {                                 // b's planes may still be in flight on its stream
         HIP_TRY(hipEventRecord(a->ev[kEvCmpWait], b->stream));
-        HIP_TRY(hipStreamWaitEvent(st, a->ev[kEvCmpWait], 0));
+        HIP_TRY(hipStreamWaitEvent(a->stream, a->ev[kEvCmpWait], 0));
     }
-    a->pin[8] = kNoBad;
-    HIP_TRY(hipMemcpyAsync(a->cmp_bad.p, a->pin + 8, 8, hipMemcpyHostToDevice, st));
-    if (T) HIP_TRY(hipMemcpyAsync(a->cmp_tiles.p, dt.data(), (size_t)T * sizeof(DivTile), hipMemcpyHostToDevice, st));
-    if (int rc = a->mark(kEvCmpZero)) return rc;
-    if (T) {
-        hipLaunchKernelGGL(div_zero_kernel, dim3((unsigned)((T * 16 + 255) / 256)), dim3(256), 0, st, a->tiles.p,
-                           a->cmp_tiles.p, T, da.window, a->cmp_rows.p);
-        HIP_TRY(hipGetLastError());
-    }
-    if (int rc = a->mark(kEvCmpTile)) return rc;
-    if (T) {
-        hipLaunchKernelGGL(cmp_tile_kernel, dim3((unsigned)T), dim3(kThreads), 0, st, a->planes.p, a->stride,
-                           b->planes.p, b->stride, a->tiles.p, a->cmp_tiles.p, da, a->cmp_rows.p, a->cmp_bad.p);
-        HIP_TRY(hipGetLastError());
-    }
-    if (int rc = a->mark(kEvCmpEnd)) return rc;
-    HIP_TRY(hipMemcpyAsync(a->pin + 8, a->cmp_bad.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));            // (dt is released)
-    const unsigned long long bad = a->pin[8];
-    MC_REQUIRE(bad == kNoBad, MC_E_RANGE,
-               "plane index %llu: A + C + G + T of a compared position is 2^26 or more in one of the samples "
-               "(dist_fix is exact below that)",
-               bad);
-    if (int rc = a->elapsed(kEvCmpZero, kEvCmpTile, &a->ms_cmp_zero)) return rc;
-    if (int rc = a->elapsed(kEvCmpTile, kEvCmpEnd, &a->ms_cmp_tile)) return rc;
-    a->cmp_first = std::move(first);
-    a->n_cmp = nw;
-    a->have_cmp = true;
-    *n_windows = nw;
-    return MC_OK;
+    const DivArgs da = div_args(window, min_depth, min_count, min_ppm);
+    return window_rows(a, a->cmp, window, da, kCmpCols, n_windows, [&](hipStream_t st) {
+        hipLaunchKernelGGL(cmp_tile_kernel, dim3((unsigned)a->n_tiles), dim3(kThreads), 0, st, a->planes.p, a->stride,
+                           b->planes.p, b->stride, a->tiles.p, a->cmp.tiles.p, da, a->cmp.rows.p, a->cmp.bad.p);
+    });
 }
 
 extern "C" int mc_bases_compare_first(const mc_bases* a, int64_t* win_first) {
     MC_REQUIRE(a && win_first, MC_E_INVALID, "null argument");
-    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
-    std::memcpy(win_first, a->cmp_first.data(), a->cmp_first.size() * 8);
-    return MC_OK;
+    return rows_first(a->cmp, win_first);
 }
 
 extern "C" int mc_bases_compare_get(const mc_bases* a, int64_t first, int64_t count, int64_t* rows) {
     MC_REQUIRE(a, MC_E_INVALID, "null argument");
-    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
-    if (int rc = check_range(first, count, a->n_cmp, "windows")) return rc;
-    MC_REQUIRE(count == 0 || rows, MC_E_INVALID, "null out");
-    if (count == 0) return MC_OK;
-    HIP_TRY(hipSetDevice(a->device));
-    HIP_TRY(hipMemcpyAsync(rows, a->cmp_rows.p + first * kCmpCols, (size_t)count * kCmpCols * 8,
-                           hipMemcpyDeviceToHost, a->stream));
-    HIP_TRY(hipStreamSynchronize(a->stream));
-    return MC_OK;
+    return rows_get(a, a->cmp, kCmpCols, first, count, rows);
 }
 
 extern "C" int mc_bases_compare_device(const mc_bases* a, const int64_t** d_rows, int64_t* n_windows) {
     MC_REQUIRE(a && d_rows && n_windows, MC_E_INVALID, "null argument");
-    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
-    *d_rows = a->cmp_rows.p;
-    *n_windows = a->n_cmp;
-    return MC_OK;
+    return rows_device(a->cmp, d_rows, n_windows);
 }
 
 extern "C" int mc_bases_compare_timing(const mc_bases* a, float* tile_ms, float* zero_ms) {
     MC_REQUIRE(a && tile_ms && zero_ms, MC_E_INVALID, "null argument");
-    MC_REQUIRE(a->have_cmp, MC_E_STATE, "no comparison computed (call mc_bases_compare)");
-    *tile_ms = a->ms_cmp_tile;
-    *zero_ms = a->ms_cmp_zero;
-    return MC_OK;
+    return rows_timing(a->cmp, tile_ms, zero_ms);
 }
 
 // ---- insertion alleles (the contract is the header's, "Insertion alleles") ----
@@ -2401,8 +2390,7 @@ extern "C" int mc_bases_ins_set(mc_bases* h, int64_t n, const int64_t* i, const 
     h->sorted_valid = false;
     invalidate_ins(h);
     h->have_cons = false;
-    h->have_div = false;
-    h->have_cmp = false;
+    drop_window_rows(h);
     HIP_TRY(h->ins_sorted.reserve((size_t)n));
     HIP_TRY(h->ins_weight.reserve((size_t)n));
     HIP_TRY(h->ins_bbase.reserve((size_t)T + 1));

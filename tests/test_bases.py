@@ -323,3 +323,46 @@ def test_abi_table_has_bases():
                  "mc_bases_sites_get", "mc_bases_dims", "mc_bases_src_open", "mc_bases_src_next",
                  "mc_bases_src_counts"):
         assert name in _lib.SIGNATURES
+
+
+def test_contig_names():
+    from metacov_amd import bases as mb
+    assert mb.contig_names(["a b", "", " ", "c_1", "x\ty z"]) == ["a", "", " ", "c_1", "x"]
+    assert mb.contig_names([]) == []
+
+
+def test_one_call_argument_errors(monkeypatch):
+    """The one-call functions' contig, range and reference errors, raised from
+    the header alone (a stand-in source: no file, no library)."""
+    from metacov_amd import bases as mb
+
+    class Header:
+        references, lengths = ["ctg_1 first", "ctg_2"], [100, 40]
+
+        def __init__(self, *a):
+            pass
+
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            pass
+
+    monkeypatch.setattr(mb, "BaseSource", Header)
+    monkeypatch.setattr(mb._lib, "load", lambda: None)
+    with pytest.raises(KeyError, match="contig 'ctg_3' is not in the header of x.bam"):
+        mb.count_coverage("x.bam", "ctg_3")
+    with pytest.raises(KeyError, match="contig 'ctg_1 first' is not in the header of x.bam"):
+        mb.count_coverage("x.bam", "ctg_1 first")           # the contig id is the name's first word
+    for start, stop, text in ((-1, 5, r"bad range \[-1, 5\)"), (7, 6, r"bad range \[7, 6\)")):
+        with pytest.raises(ValueError, match=text):
+            mb.count_coverage("x.bam", "ctg_1", start, stop)
+        with pytest.raises(ValueError, match=text):
+            mb.compare("x.bam", "y.bam", "ctg_1", start, stop)
+    with pytest.raises(ValueError, match="bad range"):
+        mb.diversity("x.bam", "ctg_2", 41)                  # the default stop is the contig's length
+    for call in (mb.diversity, mb.consensus):
+        with pytest.raises(ValueError, match="ref must have stop - start letters"):
+            call("x.bam", "ctg_2", 10, 14, ref="ACG")
+        with pytest.raises(ValueError, match="ref must have stop - start letters"):
+            call("x.bam", "ctg_2", ref=np.zeros(41, np.uint8))
